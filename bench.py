@@ -1,8 +1,13 @@
 """bench.py -- mel frames/s of the Transformer-TTS training step on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
+
+A plain run does only what the headline figure needs: set up, W warm-up steps, K timed
+steps, the result line.  --dump-outputs DIR also writes what the last timed step computed
+(dump_outputs below) as DIR/<name>.npy.  --full adds every other measurement (the ragged
+variant, the live roofline, the decode legs, the CPU baseline, the all-reduce alone).
 
 With --gpus N > 1 and no torchrun environment (WORLD_SIZE unset), this process starts the
 N rank processes itself (fresh interpreters; it makes no GPU call of its own), waits for
@@ -16,8 +21,8 @@ utterances per GPU of LJSpeech shape (phoneme 128, mel 800 x 80), synthetic
 seeded data (seed 0 + rank), random-init weights of the 52.99M-parameter
 architecture.  Weak scaling: every rank trains its own 16 utterances.
 
-Rank 0 prints ONE JSON line: value = all ranks' frames / max-over-ranks time;
-roofline = the dominant kernel (bf16 forward GEMM) measured with HIP events
+Rank 0 prints ONE JSON line: value = all ranks' frames / max-over-ranks time.
+With --full: roofline = the dominant kernel (bf16 forward GEMM) measured with HIP events
 around each launch in an instrumented step right after the timed region;
 cpu_baseline = the CPU oracle's training step on a bounded sample of the same
 workload on this box's host cores (rank 0, N = 1 only).
@@ -485,6 +490,32 @@ def longform_bench(model):
                          "algo_bytes": algo, "note": "weights per step + running utterances' KV bytes only"}}
 
 
+DUMP_SAMPLE = 1 << 21   # elements kept of each flat parameter-sized buffer (8 MB as f32)
+
+
+def snapshot_outputs(model, loss):
+    """What a caller of the timed step holds after its last call, copied to the host: the loss
+    vector the step returns, the forward outputs of that step (model.outputs) and, since the
+    step's other result is the update it applied, a fixed seeded sample (the same DUMP_SAMPLE
+    indices every run) of the flat gradient and master-weight buffers.  About 24 MB, all f32."""
+    eng = model.engine
+    mel_before, mel_after, stop, _ = model.outputs(model._last)
+    n = eng.params.numel()
+    idx = torch.randint(0, n, (min(DUMP_SAMPLE, n),), generator=torch.Generator().manual_seed(20240), dtype=torch.int64)
+    idx = idx.sort().values.to(eng.params.device)
+    out = {"loss": loss, "mel_before": mel_before, "mel_after": mel_after, "stop_logits": stop,
+           "grads_sample": eng.grads.reshape(-1)[idx], "params_sample": eng.params.reshape(-1)[idx]}
+    return {k: v.detach().float().cpu().numpy() for k, v in out.items()}
+
+
+def dump_outputs(snap: dict, path: str):
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    for k, v in snap.items():
+        np.save(os.path.join(path, k + ".npy"), v)
+    log(f"[bench] wrote {len(snap)} arrays ({sum(v.nbytes for v in snap.values()) / 1e6:.1f} MB) to {path}")
+
+
 def _free_port() -> int:
     s = socket.socket()
     s.bind(("127.0.0.1", 0))
@@ -539,11 +570,18 @@ def launch_ranks(n: int) -> int:
     return 0
 
 
-def main():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (f32): the loss "
+                         "vector, the forward outputs, a fixed sample of the gradients and of the updated weights")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run every other measurement: the cfg2 ragged variant, the live "
+                         "roofline, the cfg3 / cfg5 decode legs, the CPU baseline, the gradient all-reduce alone "
+                         "(the --no-* options below trim them; a plain run has none of them)")
     ap.add_argument("--no-graph", action="store_true", help="eager launches instead of hipGraph replay")
     ap.add_argument("--pipeline", action="store_true",
                     help="pipelined optimizer: each step's Adam at the start of the next step, beside the encoder "
@@ -554,17 +592,25 @@ def main():
     ap.add_argument("--no-longform", action="store_true", help="skip the cfg5 long-form decode measurement")
     ap.add_argument("--no-ragged", action="store_true", help="skip the cfg2 ragged-length variant")
     ap.add_argument("--profile-run", action="store_true", help="the run a rocprofv3 kernel trace is taken of: "
-                    "training step only (no ragged / decode / CPU legs, no back-to-back probe replays)")
+                    "--full with the training step and its live roofline only (no ragged / decode / CPU legs, no "
+                    "back-to-back probe replays)")
     ap.add_argument("--force-dp", action="store_true", help="dev: run the DP path (bucketed RCCL all-reduce "
                     "inside the step graph) even at world size 1")
     ap.add_argument("--dp-standin", action="store_true", help="dev: the DP path at world size 1 with each bucket's "
                     "all-reduce replaced by a kernel with an N-rank ring all-reduce's CU footprint, HBM bytes and "
                     "duration (tt2.dist.StandinGradSync; TT2_DP_STANDIN_N / _GBPS / _WG)")
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
     if args.dp_standin:
         args.force_dp = True
     if args.profile_run:
-        args.no_ragged = args.no_decode = args.no_longform = args.no_cpu_baseline = True
+        args.full = args.no_ragged = args.no_decode = args.no_longform = args.no_cpu_baseline = True
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
+
+
+def main():
+    args = parse_args()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launch_ranks(args.gpus))    # before anything touches the GPU
 
@@ -652,35 +698,39 @@ def main():
     frames = world * B_PER_GPU * TY * args.steps
     value = frames / dt
     log(f"[bench] {dt / args.steps * 1e3:.2f} ms/step, loss {lval:.4f}")
+    if args.dump_outputs and rank == 0:   # before any --full leg runs the step again
+        dump_outputs(snapshot_outputs(model, loss), args.dump_outputs)
+    full = args.full
     comm = None
     if sync is not None:   # every rank: the bucketed exchange alone (outside the timed region)
         comm = {"sync": "rccl in-graph (libtt2 communicator, comm stream inside the step graph)" if sync.in_graph
                 else "segmented (torch.distributed between graph segments)",
                 "backend": dist.get_backend(), "bucket_mb": round((sync.buckets[0][1] - sync.buckets[0][0]) * 4 / 2**20, 2),
-                "rccl_env": rccl_env(), "allreduce_alone": sync.bench_allreduce()}
+                "rccl_env": rccl_env(), "allreduce_alone": sync.bench_allreduce() if full else None}
         if args.dp_standin:
             comm["sync"] = "stand-in (one rank; per bucket a kernel with an N-rank ring all-reduce's footprint)"
             comm["standin"] = sync.params()
-        log(f"[bench] all-reduce alone: {comm['allreduce_alone']}")
+        if full:
+            log(f"[bench] all-reduce alone: {comm['allreduce_alone']}")
 
     rag = None
-    if rank == 0 and world == 1 and not args.no_ragged:
+    if full and rank == 0 and world == 1 and not args.no_ragged:
         log("[bench] cfg2 ragged variant")
         rag = ragged_bench(run, rank, max(5, args.steps // 2), bufs)
         log(f"[bench] ragged {rag['value']:.0f} valid frames/s ({rag['ms_per_step']} ms/step)")
-    rl = roofline(model, text, tl, mel, ml, replay=not args.profile_run) if rank == 0 else None
+    rl = roofline(model, text, tl, mel, ml, replay=not args.profile_run) if full and rank == 0 else None
     dec = None
-    if rank == 0 and world == 1 and not args.no_decode:
+    if full and rank == 0 and world == 1 and not args.no_decode:
         log("[bench] decode (cfg3)")
         dec = decode_bench(model)
         log(f"[bench] decode {dec['value']:.0f} frames/s ({dec['ms_per_frame_step']} ms/step)")
     lf = None
-    if rank == 0 and world == 1 and not args.no_decode and not args.no_longform:
+    if full and rank == 0 and world == 1 and not args.no_decode and not args.no_longform:
         log("[bench] long-form decode (cfg5)")
         lf = longform_bench(model)
         log(f"[bench] long-form {lf['value']:.0f} frames/s ({lf['steps_run']} steps)")
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         log("[bench] cpu baseline (oracle on host cores)")
         cpu = cpu_baseline()
         cpu["cfg1_forward"]["gpu"] = gpu_cfg1(model)
@@ -688,7 +738,7 @@ def main():
         out = {
             "metric": METRIC, "value": round(value, 1), "unit": "frames/s", "n_gpus": world, "steps": args.steps,
             "warmup": args.warmup, "ms_per_step": round(dt / args.steps * 1e3, 3), "higher_is_better": True,
-            "scaling": "weak", "vs_baseline": None, "dtype": "bf16", "data": "synthetic",
+            "scaling": "weak", "vs_baseline": None, "dtype": "bf16", "data": "synthetic", "full": full,
             "config": {"workload": ("train step (fwd+loss+bwd+STAND-IN grad exchange+Adam), LJSpeech-shape synthetic "
                                     "batch" if args.dp_standin else
                                     "train step (fwd+loss+bwd+grad all-reduce+Adam), LJSpeech-shape synthetic batch"

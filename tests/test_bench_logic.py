@@ -56,6 +56,62 @@ def test_longform_algo_bytes_counts_running_utterances_only():
     assert abs(got - want) < 1e-6 * want
 
 
+class _DumpEngine:
+    def __init__(self, n):
+        import torch
+        self.params = torch.arange(n, dtype=torch.float32)
+        self.grads = -torch.arange(n, dtype=torch.float32)
+
+
+class _DumpModel:
+    _last = "arena"
+
+    def __init__(self, n):
+        self.engine = _DumpEngine(n)
+
+    def outputs(self, A):
+        import torch
+        assert A == "arena"
+        return torch.ones(2, 3, 80), torch.full((2, 3, 80), 2.0, dtype=torch.bfloat16), torch.zeros(2, 3), None
+
+
+def test_dump_outputs_writes_f32_arrays_with_a_fixed_sample(tmp_path):
+    """--dump-outputs: every array the last step produced lands as <name>.npy in float32; the
+    parameter-sized buffers are sampled at the same sorted indices on every call (so two runs
+    compare element for element), gradients and weights at the same ones."""
+    import numpy as np
+    import torch
+    n = 3 * bench.DUMP_SAMPLE
+    m = _DumpModel(n)
+    loss = torch.tensor([4.0, 1.0, 2.0, 1.0])
+    bench.dump_outputs(bench.snapshot_outputs(m, loss), str(tmp_path / "a"))
+    bench.dump_outputs(bench.snapshot_outputs(m, loss), str(tmp_path / "b"))
+    names = {"loss", "mel_before", "mel_after", "stop_logits", "grads_sample", "params_sample"}
+    assert {f[:-4] for f in os.listdir(tmp_path / "a")} == names
+    total = 0
+    for k in names:
+        a, b = np.load(tmp_path / "a" / f"{k}.npy"), np.load(tmp_path / "b" / f"{k}.npy")
+        assert a.dtype == np.float32 and np.array_equal(a, b), k
+        total += a.nbytes
+    assert total <= 64 << 20
+    p, g = np.load(tmp_path / "a" / "params_sample.npy"), np.load(tmp_path / "a" / "grads_sample.npy")
+    assert p.shape == (bench.DUMP_SAMPLE,) and np.all(np.diff(p) >= 0) and 0 <= p[0] and p[-1] < n
+    assert np.array_equal(g, -p)                     # the same indices of both buffers
+    assert np.load(tmp_path / "a" / "mel_after.npy")[0, 0, 0] == 2.0
+    assert np.array_equal(np.load(tmp_path / "a" / "loss.npy"), loss.numpy())
+
+
+def test_plain_run_has_no_extra_legs_unless_full():
+    """The options a plain run is defined by: --full is off by default, and the profile run
+    (which reports the live roofline) turns it on."""
+    plain = bench.parse_args(["--gpus", "1", "--steps", "3", "--warmup", "2"])
+    assert not plain.full and plain.dump_outputs is None and (plain.steps, plain.warmup) == (3, 2)
+    assert bench.parse_args(["--full"]).full
+    prof = bench.parse_args(["--profile-run"])
+    assert prof.full and prof.no_ragged and prof.no_decode and prof.no_cpu_baseline
+    assert bench.parse_args(["--dump-outputs", "d"]).dump_outputs == "d"
+
+
 def test_multi_gpu_request_without_torchrun_spawns_ranks_and_fails_loudly():
     """`bench.py --gpus 2` with no WORLD_SIZE starts 2 rank processes itself.  Here (no GPU)
     the ranks rendezvous over gloo and then fail at their first device call: the launcher

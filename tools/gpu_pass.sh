@@ -28,16 +28,16 @@ for s in $STEPS; do
     dpt) run dpt 200 600 python -u -m pytest tests/test_gpu_dist.py tests/test_gpu_syncbn.py tests/test_gpu_norm.py \
            tests/test_gpu_overlap.py tests/test_gpu_decode.py tests/test_gpu_fullsize.py tests/test_gpu_metrics.py \
            -x -v --timeout 300 --timeout-method thread > "$OUT/dpt_tests.log" 2>&1 ;;
-    bench) run bench 150 420 python -u bench.py > "$OUT/bench.json" 2> "$OUT/bench.err" ;;
+    bench) run bench 150 420 python -u bench.py --full > "$OUT/bench.json" 2> "$OUT/bench.err" ;;
     ab) for i in 1 2; do
           for e in TT2_WGRAD_OVERLAP=0 TT2_WGRAD_OVERLAP=1; do
-            run "ab $e" 90 200 env $e python -u bench.py --steps 30 --warmup 5 --no-cpu-baseline --no-decode \
+            run "ab $e" 90 200 env $e python -u bench.py --steps 30 --warmup 5 --full --no-cpu-baseline --no-decode \
               > "$OUT/ab_run.json" 2> "$OUT/ab_run.err"
             echo "$e $(lastms "$OUT/ab_run.json")" >> "$OUT/ab.txt"
           done
         done ;;
     knobs) for e in ${KNOBS:-TT2_SIDE_WG=128 TT2_SIDE_SPLIT=2 TT2_SIDE_START=1 TT2_SIDE_START=3 TT2_WGRAD_OVERLAP=1}; do
-             run "knob $e" 90 200 env ${e//,/ } python -u bench.py --steps 30 --warmup 5 --no-cpu-baseline --no-decode \
+             run "knob $e" 90 200 env ${e//,/ } python -u bench.py --steps 30 --warmup 5 --full --no-cpu-baseline --no-decode \
                > "$OUT/ab_run.json" 2> "$OUT/ab_run.err"
              echo "$e $(lastms "$OUT/ab_run.json")" >> "$OUT/knobs.txt"
            done ;;
@@ -52,7 +52,7 @@ for s in $STEPS; do
             done ;;
     stepab) for i in 1 2; do
               for lib in abl/${STEPAB_OLD:-attn0}.so transformer-tacotron2_amd/tt2/libtt2.so; do
-                run "stepab $lib" 90 200 env TT2_LIB=$lib python -u bench.py --steps 30 --warmup 5 --no-cpu-baseline \
+                run "stepab $lib" 90 200 env TT2_LIB=$lib python -u bench.py --steps 30 --warmup 5 --full --no-cpu-baseline \
                   --no-decode > "$OUT/ab_run.json" 2> "$OUT/ab_run.err"
                 echo "$lib $(lastms "$OUT/ab_run.json")" >> "$OUT/stepab.txt"
               done
@@ -91,11 +91,11 @@ for s in $STEPS; do
              done
            done ;;
     pmc) run pmc_f 120 300 rocprofv3 --pmc FETCH_SIZE -d "$OUT/pmc_fetch" -o run --output-format csv -- \
-           python3 bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-decode > "$OUT/bench_fetch.json" 2> "$OUT/bench_fetch.err"
+           python3 bench.py --steps 5 --warmup 2 --full --no-cpu-baseline --no-decode > "$OUT/bench_fetch.json" 2> "$OUT/bench_fetch.err"
          run pmc_w 120 300 rocprofv3 --pmc WRITE_SIZE -d "$OUT/pmc_write" -o run --output-format csv -- \
-           python3 bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-decode > "$OUT/bench_write.json" 2> "$OUT/bench_write.err" ;;
+           python3 bench.py --steps 5 --warmup 2 --full --no-cpu-baseline --no-decode > "$OUT/bench_write.json" 2> "$OUT/bench_write.err" ;;
     mfma) run mfma 120 300 rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE -d "$OUT/mfma" -o run \
-            --output-format csv -- python3 bench.py --steps 3 --warmup 1 --no-decode --no-cpu-baseline --no-ragged \
+            --output-format csv -- python3 bench.py --steps 3 --warmup 1 --full --no-decode --no-cpu-baseline --no-ragged \
             > "$OUT/bench_mfma.json" 2> "$OUT/bench_mfma.err" ;;
     dpmc) run dpmc_f 120 300 rocprofv3 --pmc FETCH_SIZE -d "$OUT/dtr/fetch" -o run --output-format csv -- \
             python3 tools/decode_traffic.py --out="$OUT/dtr" > "$OUT/dtr_fetch.log" 2>&1
@@ -118,13 +118,13 @@ for s in $STEPS; do
     pkgab) for i in 1 2 3; do   # host-schedule A/B: abl/pkg_<name>/tt2 (a copy of the package at an older commit)
              for pk in abl/pkg_${PKGAB_OLD:-head} ""; do
                run "pkgab $pk" 90 200 env TT2_PKG=$pk TT2_LIB=$PWD/transformer-tacotron2_amd/tt2/libtt2.so python -u \
-                 bench.py --steps 30 --warmup 5 --no-cpu-baseline --no-decode > "$OUT/ab_run.json" 2> "$OUT/ab_run.err"
+                 bench.py --steps 30 --warmup 5 --full --no-cpu-baseline --no-decode > "$OUT/ab_run.json" 2> "$OUT/ab_run.err"
                echo "${pk:-current} $(lastms "$OUT/ab_run.json")" >> "$OUT/pkgab.txt"
              done
            done ;;
     dpab) for i in 1 2; do   # DP schedule on one GPU: no exchange / 1-rank RCCL in-graph / N-rank stand-in
             for m in "" "--force-dp" "--dp-standin"; do
-              run "dpab $m" 90 200 python -u bench.py --steps 30 --warmup 5 --no-cpu-baseline --no-decode --no-ragged \
+              run "dpab $m" 90 200 python -u bench.py --steps 30 --warmup 5 --full --no-cpu-baseline --no-decode --no-ragged \
                 $m > "$OUT/ab_run.json" 2> "$OUT/ab_run.err"
               echo "${m:-plain} $(lastms "$OUT/ab_run.json")" >> "$OUT/dpab.txt"
             done
@@ -132,31 +132,31 @@ for s in $STEPS; do
     bucketab) for i in 1 2; do   # bucket size under the stand-in (and the 1-rank RCCL path)
                 for mb in ${BUCKETS:-25 12.5 8}; do
                   for m in ${BUCKET_MODES:---dp-standin}; do
-                    run "bucketab $mb $m" 90 200 env TT2_BUCKET_MB=$mb python -u bench.py --steps 30 --warmup 5 \
+                    run "bucketab $mb $m" 90 200 env TT2_BUCKET_MB=$mb python -u bench.py --steps 30 --warmup 5 --full \
                       --no-cpu-baseline --no-decode --no-ragged $m > "$OUT/ab_run.json" 2> "$OUT/ab_run.err"
                     echo "$mb $m $(lastms "$OUT/ab_run.json")" >> "$OUT/bucketab.txt"
                   done
                 done
               done ;;
     modeab) for i in 1 2; do   # layer-aligned vs fixed-size DP buckets, no-DP step beside them
-              run "modeab plain" 90 200 python -u bench.py --steps 30 --warmup 5 --no-cpu-baseline --no-decode \
+              run "modeab plain" 90 200 python -u bench.py --steps 30 --warmup 5 --full --no-cpu-baseline --no-decode \
                 --no-ragged > "$OUT/ab_run.json" 2> "$OUT/ab_run.err"
               echo "plain $(lastms "$OUT/ab_run.json")" >> "$OUT/modeab.txt"
               for mode in layers fixed; do
                 for m in --dp-standin --force-dp; do
-                  run "modeab $mode $m" 90 200 env TT2_BUCKET_MODE=$mode python -u bench.py --steps 30 --warmup 5 \
+                  run "modeab $mode $m" 90 200 env TT2_BUCKET_MODE=$mode python -u bench.py --steps 30 --warmup 5 --full \
                     --no-cpu-baseline --no-decode --no-ragged $m > "$OUT/ab_run.json" 2> "$OUT/ab_run.err"
                   echo "$mode $m $(lastms "$OUT/ab_run.json")" >> "$OUT/modeab.txt"
                 done
               done
             done ;;
     deferab) for i in 1 2; do   # bucket hand-off right after its side job (0) or after the next one (1)
-               run "deferab plain" 90 200 python -u bench.py --steps 30 --warmup 5 --no-cpu-baseline --no-decode \
+               run "deferab plain" 90 200 python -u bench.py --steps 30 --warmup 5 --full --no-cpu-baseline --no-decode \
                  --no-ragged > "$OUT/ab_run.json" 2> "$OUT/ab_run.err"
                echo "plain $(lastms "$OUT/ab_run.json")" >> "$OUT/deferab.txt"
                for dfr in 0 1; do
                  for m in --dp-standin --force-dp; do
-                   run "deferab $dfr $m" 90 200 env TT2_DEFER_FORK=$dfr python -u bench.py --steps 30 --warmup 5 \
+                   run "deferab $dfr $m" 90 200 env TT2_DEFER_FORK=$dfr python -u bench.py --steps 30 --warmup 5 --full \
                      --no-cpu-baseline --no-decode --no-ragged $m > "$OUT/ab_run.json" 2> "$OUT/ab_run.err"
                    echo "defer=$dfr $m $(lastms "$OUT/ab_run.json")" >> "$OUT/deferab.txt"
                  done

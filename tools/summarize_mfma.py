@@ -1,7 +1,7 @@
 """MFMA-busy evidence from a rocprofv3 PMC pass (dev tool, CPU):
 
     rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE -d gpurun_out/prof_mfma -o run \
-        --output-format csv -- python3 bench.py --steps 3 --warmup 1 --no-decode --no-cpu-baseline --no-ragged
+        --output-format csv -- python3 bench.py --steps 3 --warmup 1 --full --no-decode --no-cpu-baseline --no-ragged
     python tools/summarize_mfma.py gpurun_out/prof_mfma/run_counter_collection.csv profiles/r01g_mfma_busy.json
 
 Per kernel: mean SQ_VALU_MFMA_BUSY_CYCLES per launch (summed over the chip's SIMDs), the
