@@ -217,6 +217,43 @@ int tt2_attn_probs(const tt2_attn_args* a, float* probs, hipStream_t stream);
 int tt2_attn_fwd(const tt2_attn_args* a, hipStream_t stream);
 int tt2_attn_bwd(const tt2_attn_args* a, hipStream_t stream);
 
+/* Guided attention (diagonal loss on encoder-decoder attention, SpeechT5 / ESPnet convention),
+ * folded into the non-causal forward and backward.  For utterance b with Tx = min(tk,
+ * key_len[b]) visible keys and Ty = min(tq, q_len[b]) valid query rows,
+ *   W[n, t] = 1 - exp(-(t / Tx - n / Ty)^2 / (2 sigma^2)),
+ * the forward also stores g[n] = sum_t P[n, t] W[n, t] into rows ([batch*heads, tq] f32; exactly 0
+ * for heads >= `heads`, rows n >= Ty and rows with no visible key), and the backward differentiates
+ * out + kappa * sum g:  dS = P (dP + kappa W - (delta + kappa g))  on those heads and rows, with
+ * kappa read from device memory (coef; tt2_guided_attn_loss writes it).  o_out and lse of the guided
+ * forward equal tt2_attn_fwd's bit for bit; the guided backward leaves delta + kappa g in the delta
+ * scratch.  Causal launches are refused (TT2_E_INVALID).  Same variants and parts as the plain
+ * calls. */
+typedef struct tt2_attn_guide {
+  const int32_t* q_len;   /* [batch] valid query rows (may be NULL: tq) */
+  float* rows;            /* g, [batch*heads, tq] f32: written by fwd, read by bwd */
+  const float* coef;      /* device kappa (bwd only) */
+  float sigma;
+  int32_t heads;          /* heads h < heads are guided (0 <= heads <= the attention's heads) */
+} tt2_attn_guide;
+int tt2_attn_fwd_guided(const tt2_attn_args* a, const tt2_attn_guide* g, hipStream_t stream);
+int tt2_attn_bwd_guided(const tt2_attn_args* a, const tt2_attn_guide* g, hipStream_t stream);
+
+/* The guided-attention term of a step, one fixed-order reduction launch (no atomics):
+ *   N     = n_layers * guide_heads * sum_b Tx_b * Ty_b   (from the device lengths)
+ *   term  = scale * (sum of rows[l] over the guided heads) / N     (0 if N = 0)
+ *   coef  = scale * grad_scale / N   (kappa for tt2_attn_bwd_guided; 0 if N = 0)
+ *   loss_out[0] += term              (loss_out may be NULL) */
+#define TT2_GUIDE_MAX_LAYERS 16
+typedef struct tt2_guide_loss_args {
+  const float* rows[TT2_GUIDE_MAX_LAYERS];   /* the guided layers' g buffers, [batch*heads, tq] f32 each */
+  const int32_t* key_len; const int32_t* q_len;   /* [batch], device (NULL: tk / tq) */
+  float* loss_out; float* term; float* coef;
+  int32_t n_layers, batch, heads, guide_heads, tq, tk;
+  float scale;
+  float grad_scale;   /* multiplies kappa (1/world_size under data parallelism) */
+} tt2_guide_loss_args;
+int tt2_guided_attn_loss(const tt2_guide_loss_args* a, hipStream_t stream);
+
 /* ------------------------------------------------------------------ decode
  * One query row per batch element (the AR decode step):
  * out[b*o_ld + 64h ..] = softmax(scale q k^T) v over keys j < n_b of batch b,

@@ -21,6 +21,7 @@
 // attn_bwd_prep (f32 / v1 path) or from the v3 dQ kernel, which runs first.
 #include <math.h>
 
+#include <string>
 #include <type_traits>
 
 #include "tt2_capi.h"
@@ -71,6 +72,15 @@ struct AttnArgs {
   int B, H, Tq, Tk, causal;
   float scale;
 };
+// the guided (G) instantiations' kernel argument: the same plus tt2_attn_guide
+struct AttnArgsG : AttnArgs {
+  const int32_t* q_len;   // valid query rows per batch (NULL: Tq)
+  float* grow;            // [B*H, Tq] g = sum_t P W of each row (forward writes, backward reads)
+  const float* gcoef;     // device kappa (backward)
+  float gk;               // log2(e) / (2 sigma^2)
+  int gheads;             // heads h < gheads are guided
+};
+template <bool G> using ArgsT = std::conditional_t<G, AttnArgsG, AttnArgs>;
 
 TT2_DEV int key_limit(const AttnArgs& a, int b) {
   int kl = a.Tk;
@@ -78,9 +88,35 @@ TT2_DEV int key_limit(const AttnArgs& a, int b) {
   return kl < 0 ? 0 : kl;
 }
 
+// Guided attention (diagonal loss on the cross-attention, G instantiations): the weight of
+// query n, key t of utterance b is W[n, t] = 1 - exp(-(t / Tx_b - n / Ty_b)^2 / (2 sigma^2)),
+// Tx_b the visible keys and Ty_b the valid query rows.  Evaluated in registers from the lane's
+// indices: tk = t * rk, nq = n * rq, one exp2 with log2(e) / (2 sigma^2) folded into gk.
+struct Guide {
+  float rk, rq;   // 1 / Tx_b, 1 / Ty_b (0 for an empty utterance)
+  int qlim;       // Ty_b
+  bool sel;       // this block's head is guided (block-uniform)
+};
+TT2_DEV Guide guide_of(const AttnArgsG& a, int b, int h, int klim) {
+  Guide g;
+  int ql = a.Tq;
+  if (a.q_len) ql = min(ql, a.q_len[b]);
+  g.qlim = ql < 0 ? 0 : ql;
+  // block-uniform, but computed by the vector ALU: moved to scalar registers by hand
+  g.rk = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(klim > 0 ? 1.f / (float)klim : 0.f)));
+  g.rq = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(g.qlim > 0 ? 1.f / (float)g.qlim : 0.f)));
+  g.sel = h < a.gheads && klim > 0 && g.qlim > 0;
+  return g;
+}
+template <bool FAST> TT2_DEV float guide_w(float tk, float nq, float gk) {
+  const float x = tk - nq;
+  const float e = -(x * x) * gk;
+  return 1.f - (FAST ? __builtin_amdgcn_exp2f(e) : exp2f(e));
+}
+
 // ----------------------------------------------------------------- forward
-template <typename T>
-__global__ __launch_bounds__(NT) void attn_fwd_kernel(AttnArgs a) {
+template <typename T, bool G>
+__global__ __launch_bounds__(NT) void attn_fwd_kernel(ArgsT<G> a) {
   constexpr int LD = LdsLd<T>::V;
   __shared__ __attribute__((aligned(16))) T sK[BKV * LD];
   __shared__ __attribute__((aligned(16))) T sV[BKV * LD];
@@ -115,6 +151,13 @@ __global__ __launch_bounds__(NT) void attn_fwd_kernel(AttnArgs a) {
   int kend = klim;
   if (a.causal) kend = min(kend, q0 + BQ);
   T* myP = sP + w * 16 * LD;
+  Guide gd = {};
+  float gk = 0.f;
+  float g_r[4] = {0.f, 0.f, 0.f, 0.f};   // G: sum_t p W beside l_r
+  if constexpr (G) {
+    gd = guide_of(a, b, h, klim);
+    gk = a.gk;
+  }
 
   for (int k0 = 0; k0 < kend; k0 += BKV) {
     __syncthreads();
@@ -163,6 +206,16 @@ __global__ __launch_bounds__(NT) void attn_fwd_kernel(AttnArgs a) {
       }
       l_r[r] = l_r[r] * alpha + sum16(rs);
       m_r[r] = mn;
+      if constexpr (G) {
+        if (gd.sel) {   // p W in f32, before p is rounded for the P V product
+          const float nq = (float)(q0 + 16 * w + 4 * hq + r) * gd.rq;
+          float gs = 0.f;
+#pragma unroll
+          for (int jb = 0; jb < 4; ++jb)
+            gs += s[jb][r] * guide_w<false>((float)(k0 + 16 * jb + row_l) * gd.rk, nq, gk);
+          g_r[r] = g_r[r] * alpha + sum16(gs);
+        }
+      }
 #pragma unroll
       for (int jd = 0; jd < 4; ++jd) o[jd][r] *= alpha;
     }
@@ -197,13 +250,18 @@ __global__ __launch_bounds__(NT) void attn_fwd_kernel(AttnArgs a) {
     for (int jd = 0; jd < 4; ++jd) O[(int64_t)qr * a.o_ld + 16 * jd + row_l] = from_f32<T>(o[jd][r] * inv);
     if (row_l == 0)
       a.lse[(int64_t)bh * a.Tq + qr] = l_r[r] > 0.f ? m_r[r] + log2f(l_r[r]) : INFINITY;
+    if constexpr (G) {
+      if (row_l == 0)
+        a.grow[(int64_t)bh * a.Tq + qr] = gd.sel && qr < gd.qlim && l_r[r] > 0.f ? g_r[r] / l_r[r] : 0.f;
+    }
   }
 }
 
 // ---------------------------------------------------------------- backward
 // delta[bh, t] = sum_d dO[t, h*64 + d] * O[t, h*64 + d]; one wave per (b, t) row, all heads.
-template <typename T>
-__global__ __launch_bounds__(NT) void attn_bwd_prep_kernel(AttnArgs a) {
+// G: delta + kappa g for the guided rows, so dS = P (dP + kappa W - delta) downstream
+template <typename T, bool G>
+__global__ __launch_bounds__(NT) void attn_bwd_prep_kernel(ArgsT<G> a) {
   const int lane = threadIdx.x & 63;
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6);  // b * Tq + t
   if (row >= a.B * a.Tq) return;
@@ -222,12 +280,18 @@ __global__ __launch_bounds__(NT) void attn_bwd_prep_kernel(AttnArgs a) {
     s += __shfl_xor(s, 1, 64);
     s += __shfl_xor(s, 2, 64);
     s += __shfl_xor(s, 4, 64);
+    if constexpr (G) {
+      if ((lane & 7) == 0 && h < a.H) {
+        const Guide gd = guide_of(a, b, h, key_limit(a, b));
+        if (gd.sel && t < gd.qlim) s += *a.gcoef * a.grow[((int64_t)b * a.H + h) * a.Tq + t];
+      }
+    }
     if ((lane & 7) == 0 && h < a.H) a.delta[((int64_t)b * a.H + h) * a.Tq + t] = s;
   }
 }
 
-template <typename T>
-__global__ __launch_bounds__(NT) void attn_bwd_dq_kernel(AttnArgs a) {
+template <typename T, bool G>
+__global__ __launch_bounds__(NT) void attn_bwd_dq_kernel(ArgsT<G> a) {
   constexpr int LD = LdsLd<T>::V;
   __shared__ __attribute__((aligned(16))) T sK[BKV * LD];
   __shared__ __attribute__((aligned(16))) T sV[BKV * LD];
@@ -268,6 +332,20 @@ __global__ __launch_bounds__(NT) void attn_bwd_dq_kernel(AttnArgs a) {
   int kend = klim;
   if (a.causal) kend = min(kend, q0 + BQ);
   T* myP = sP + w * 16 * LD;
+  Guide gd = {};
+  float gk = 0.f;
+  float kap[4] = {0.f, 0.f, 0.f, 0.f}, nq[4] = {0.f, 0.f, 0.f, 0.f};   // G: kappa of the valid rows (else 0), n / Ty
+  if constexpr (G) {
+    gd = guide_of(a, b, h, klim);
+    gk = a.gk;
+    const float kappa = gd.sel ? *a.gcoef : 0.f;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int qr = q0 + 16 * w + 4 * hq + r;
+      kap[r] = qr < gd.qlim ? kappa : 0.f;
+      nq[r] = (float)qr * gd.rq;
+    }
+  }
 
   for (int k0 = 0; k0 < kend; k0 += BKV) {
     __syncthreads();
@@ -296,7 +374,9 @@ __global__ __launch_bounds__(NT) void attn_bwd_dq_kernel(AttnArgs a) {
         const int qr = q0 + 16 * w + 4 * hq + r;
         float p = exp2f(s[jb][r] * c - lse[r]);
         if (key >= klim || (a.causal && key > qr)) p = 0.f;
-        const float ds = p * (dp[jb][r] - dl[r]);
+        float ds;
+        if (G && gd.sel) ds = p * (fmaf(kap[r], guide_w<false>((float)key * gd.rk, nq[r], gk), dp[jb][r]) - dl[r]);
+        else ds = p * (dp[jb][r] - dl[r]);
         myP[(4 * hq + r) * LD + 16 * jb + row_l] = from_f32<T>(ds);
       }
     }
@@ -324,8 +404,8 @@ __global__ __launch_bounds__(NT) void attn_bwd_dq_kernel(AttnArgs a) {
   }
 }
 
-template <typename T>
-__global__ __launch_bounds__(NT) void attn_bwd_dkdv_kernel(AttnArgs a) {
+template <typename T, bool G>
+__global__ __launch_bounds__(NT) void attn_bwd_dkdv_kernel(ArgsT<G> a) {
   constexpr int LD = LdsLd<T>::V;
   __shared__ __attribute__((aligned(16))) T sQ[BQ * LD];
   __shared__ __attribute__((aligned(16))) T sdO[BQ * LD];
@@ -361,6 +441,16 @@ __global__ __launch_bounds__(NT) void attn_bwd_dkdv_kernel(AttnArgs a) {
   T* myP = sP + w * 16 * LD;
   const bool block_live = k0 < klim;
   const int qstart = (a.causal ? (k0 / BQ) * BQ : 0);
+  Guide gd = {};
+  float gk = 0.f;
+  float kappa = 0.f, tk[4] = {0.f, 0.f, 0.f, 0.f};   // G: t / Tx of the lane's keys
+  if constexpr (G) {
+    gd = guide_of(a, b, h, klim);
+    gk = a.gk;
+    kappa = gd.sel ? *a.gcoef : 0.f;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) tk[r] = (float)(k0 + 16 * w + 4 * hq + r) * gd.rk;
+  }
 
   for (int q0 = qstart; block_live && q0 < a.Tq; q0 += BQ) {
     __syncthreads();
@@ -422,10 +512,17 @@ __global__ __launch_bounds__(NT) void attn_bwd_dkdv_kernel(AttnArgs a) {
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
     // dS^T = P^T (dP^T - delta) -> LDS, dK += dS^T Q
 #pragma unroll
-    for (int jb = 0; jb < 4; ++jb)
+    for (int jb = 0; jb < 4; ++jb) {
+      const int qc = q0 + 16 * jb + row_l;
+      const float kq = G && qc < gd.qlim ? kappa : 0.f, nq = (float)qc * gd.rq;
 #pragma unroll
-      for (int r = 0; r < 4; ++r)
-        myP[(4 * hq + r) * LD + 16 * jb + row_l] = from_f32<T>(pv[jb][r] * (dp[jb][r] - dl[jb]));
+      for (int r = 0; r < 4; ++r) {
+        float ds;
+        if (G && gd.sel) ds = pv[jb][r] * (fmaf(kq, guide_w<false>(tk[r], nq, gk), dp[jb][r]) - dl[jb]);
+        else ds = pv[jb][r] * (dp[jb][r] - dl[jb]);
+        myP[(4 * hq + r) * LD + 16 * jb + row_l] = from_f32<T>(ds);
+      }
+    }
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
@@ -588,8 +685,10 @@ TT2_DEV void zero16(f32x16& x) {
 #define ATTN_STAMP(slot)
 #endif
 
-template <int NW>
-__global__ __launch_bounds__(NW * 64) void attn_fwd3_kernel(AttnArgs a) {
+// G (guided, non-causal only): g = sum_t P W of the lane's query row accumulates beside l_r
+// (same alpha, same two-half combine, same 1 / l) and is stored to a.grow
+template <int NW, bool G>
+__global__ __launch_bounds__(NW * 64) void attn_fwd3_kernel(ArgsT<G> a) {
   constexpr int NTH = NW * 64, PER = Stage3<NTH>::PER, QB = 32 * NW;
   __shared__ __attribute__((aligned(16))) bf16 sK[2][64 * D];
   __shared__ __attribute__((aligned(16))) bf16 sV[2][64 * D];
@@ -618,6 +717,14 @@ __global__ __launch_bounds__(NW * 64) void attn_fwd3_kernel(AttnArgs a) {
   int kend = klim;
   if (a.causal) kend = min(kend, q0 + QB);
   const int ntile = kend > 0 ? (kend + 63) / 64 : 0;
+  Guide gd = {};
+  float gk = 0.f;
+  float g_r = 0.f, nq = 0.f;
+  if constexpr (G) {
+    gd = guide_of(a, b, h, klim);
+    gk = a.gk;
+    nq = (float)qv * gd.rq;
+  }
   uint4 rk[PER], rv[PER];
   if (ntile > 0) {
     g2r3<NTH>(rk, K, 0, tid);
@@ -668,20 +775,37 @@ __global__ __launch_bounds__(NW * 64) void attn_fwd3_kernel(AttnArgs a) {
       if (__any(mn != m_r)) {   // exact: skipped lanes would multiply by 1
         const float alpha = fast_exp2(m_r - base);
         l_r *= alpha;
+        if constexpr (G) g_r *= alpha;
 #pragma unroll
         for (int db = 0; db < 2; ++db) o[db] *= alpha;
       }
       m_r = mn;
       bf16x8 pf[2][2];
       float rs = 0.f;
+      if (G && gd.sel) {   // block-uniform: the same p, and p W in f32 before p is rounded
+        float gs = 0.f;
 #pragma unroll
-      for (int kb = 0; kb < 2; ++kb)
+        for (int kb = 0; kb < 2; ++kb) {
+          const float t0 = (float)(k0 + 32 * kb + 4 * hi);
 #pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const float p = fast_exp2(fmaf(s[kb][r], c, -base));
-          rs += p;
-          pf[kb][r >> 3][r & 7] = (bf16)p;
+          for (int r = 0; r < 16; ++r) {
+            const float p = fast_exp2(fmaf(s[kb][r], c, -base));
+            rs += p;
+            gs = fmaf(p, guide_w<true>((t0 + (float)crow(r, 0)) * gd.rk, nq, gk), gs);
+            pf[kb][r >> 3][r & 7] = (bf16)p;
+          }
         }
+        g_r += gs;
+      } else {
+#pragma unroll
+        for (int kb = 0; kb < 2; ++kb)
+#pragma unroll
+          for (int r = 0; r < 16; ++r) {
+            const float p = fast_exp2(fmaf(s[kb][r], c, -base));
+            rs += p;
+            pf[kb][r >> 3][r & 7] = (bf16)p;
+          }
+      }
       l_r += rs;
 #pragma unroll
       for (int kb = 0; kb < 2; ++kb)
@@ -708,14 +832,18 @@ __global__ __launch_bounds__(NW * 64) void attn_fwd3_kernel(AttnArgs a) {
     store_rowT(O + (int64_t)qv * a.o_ld, o, l > 0.f ? 1.f / l : 0.f, hi);
     if (hi == 0) a.lse[(int64_t)bh * a.Tq + qv] = l > 0.f ? m_r + log2f(l) : INFINITY;
   }
+  if constexpr (G) {
+    const float gsum = xor32_sum(g_r);
+    if (qv < a.Tq && hi == 0) a.grow[(int64_t)bh * a.Tq + qv] = gd.sel && qv < gd.qlim && l > 0.f ? gsum / l : 0.f;
+  }
 }
 
 // dQ: wave = 32 queries (query on the lane), workgroup walks 64-key tiles in two
 // 32-key halves.
-template <int NW>
+template <int NW, bool G>
 // dQ body (also the fused dQ + dK/dV launch): workgroup (bx, by) of a (B*H, ny) grid; smem
 // holds sK[2][64 D] and sV[2][64 D]; publish: store delta = rowsum(dO * O) for a later dK/dV
-TT2_DEV void attn_bwd_dq3_body(const AttnArgs& a, int bx, int by, int ny, char* smem, bool publish) {
+TT2_DEV void attn_bwd_dq3_body(const ArgsT<G>& a, int bx, int by, int ny, char* smem, bool publish) {
   constexpr int NTH = NW * 64, PER = Stage3<NTH>::PER, QB = 32 * NW;
   bf16 (*sK)[64 * D] = reinterpret_cast<bf16 (*)[64 * D]>(smem);
   bf16 (*sV)[64 * D] = reinterpret_cast<bf16 (*)[64 * D]>(smem + 2 * 64 * D * sizeof(bf16));
@@ -740,6 +868,20 @@ TT2_DEV void attn_bwd_dq3_body(const AttnArgs& a, int bx, int by, int ny, char* 
   const RowBuf Ob = row_buf(reinterpret_cast<const bf16*>(a.o) + (int64_t)b * a.Tq * a.o_ld + h * D, a.o_ld, a.Tq);
   own_frags(fo, Ob, qv, hi);
   const float lse = qok ? a.lse[(int64_t)bh * a.Tq + qv] : INFINITY;
+  // G: dS = P (dP + kappa W - (delta + kappa g)) on the guided heads' valid rows; kap is 0 on
+  // every other row, and the published delta carries the kappa g term for the dK / dV kernel
+  Guide gd = {};
+  float gk = 0.f;
+  float kap = 0.f, nq = 0.f, kg = 0.f;
+  if constexpr (G) {
+    gd = guide_of(a, b, h, key_limit(a, b));
+    gk = a.gk;
+    if (gd.sel) {
+      kap = qv < gd.qlim ? *a.gcoef : 0.f;
+      nq = (float)qv * gd.rq;
+      kg = qok ? kap * a.grow[(int64_t)bh * a.Tq + qv] : 0.f;
+    }
+  }
   TT2_VMCNT0();   // Q / dO / O fragments and the LSE are final before the tile loop
   float dsum = 0.f;
 #pragma unroll
@@ -747,6 +889,7 @@ TT2_DEV void attn_bwd_dq3_body(const AttnArgs& a, int bx, int by, int ny, char* 
 #pragma unroll
     for (int j = 0; j < 8; ++j) dsum += (float)fdo[st][j] * (float)fo[st][j];
   dsum += __shfl_xor(dsum, 32, 64);
+  if constexpr (G) dsum += kg;
   const float dl = qok ? dsum : 0.f;
   if (publish && qok && hi == 0) a.delta[(int64_t)bh * a.Tq + qv] = dsum;
   const float c = a.scale * LOG2E;
@@ -797,8 +940,17 @@ TT2_DEV void attn_bwd_dq3_body(const AttnArgs& a, int bx, int by, int ny, char* 
         for (int r = 0; r < 16; ++r) p[r] = crow(r, 0) > lim ? 0.f : p[r];
       }
       bf16x8 dsf[2];
+      if (G && gd.sel) {   // block-uniform
+        const float t0 = (float)(kb0 + 4 * hi);
 #pragma unroll
-      for (int r = 0; r < 16; ++r) dsf[r >> 3][r & 7] = (bf16)(p[r] * (dp[r] - dl));
+        for (int r = 0; r < 16; ++r) {
+          const float wgt = guide_w<true>((t0 + (float)crow(r, 0)) * gd.rk, nq, gk);
+          dsf[r >> 3][r & 7] = (bf16)(p[r] * (fmaf(kap, wgt, dp[r]) - dl));
+        }
+      } else {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) dsf[r >> 3][r & 7] = (bf16)(p[r] * (dp[r] - dl));
+      }
 #pragma unroll
       for (int hh = 0; hh < 2; ++hh)
 #pragma unroll
@@ -819,17 +971,21 @@ TT2_DEV void attn_bwd_dq3_body(const AttnArgs& a, int bx, int by, int ny, char* 
 
 // dK, dV: wave = 32 keys (key on the lane), workgroup walks 64-query tiles in two
 // 32-query halves.
-template <int NW>
+template <int NW, bool G>
 // dK / dV body: workgroup (bx, by) of a (B*H, key blocks) grid; smem holds sQ[2][64 D],
 // sdO[2][64 D], sL[2][64], sDl[2][64]; reads delta (published by the dQ pass or attn_bwd_prep)
 // self_delta: compute delta = rowsum(dO * O) of each staged query tile here (from the dO
 // chunks already in registers and the matching O chunks) instead of reading a.delta
-TT2_DEV void attn_bwd_dkdv3_body(const AttnArgs& a, int bx, int by, char* smem, bool self_delta) {
+// G: dS gains kappa W on the guided heads' valid query rows.  The published delta already
+// carries kappa g; with self_delta, kappa g of each staged row is loaded with its LSE and
+// staged through sG[2][64] (after sDl)
+TT2_DEV void attn_bwd_dkdv3_body(const ArgsT<G>& a, int bx, int by, char* smem, bool self_delta) {
   constexpr int NTH = NW * 64, PER = Stage3<NTH>::PER, KB = 32 * NW;
   bf16 (*sQ)[64 * D] = reinterpret_cast<bf16 (*)[64 * D]>(smem);
   bf16 (*sdO)[64 * D] = reinterpret_cast<bf16 (*)[64 * D]>(smem + 2 * 64 * D * sizeof(bf16));
   float (*sL)[64] = reinterpret_cast<float (*)[64]>(smem + 4 * 64 * D * sizeof(bf16));
   float (*sDl)[64] = reinterpret_cast<float (*)[64]>(smem + 4 * 64 * D * sizeof(bf16) + 2 * 64 * sizeof(float));
+  float (*sG)[64] = reinterpret_cast<float (*)[64]>(smem + 4 * 64 * D * sizeof(bf16) + 4 * 64 * sizeof(float));
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const int kl = lane & 31, hi = lane >> 5;
   const int bh = bx, b = bh / a.H, h = bh % a.H;   // x = (batch, head): block index on y
@@ -859,6 +1015,17 @@ TT2_DEV void attn_bwd_dkdv3_body(const AttnArgs& a, int bx, int by, char* smem, 
   const int klim = key_limit(a, b);
   const int qstart = a.causal ? (k0 / 64) * 64 : 0;
   const int ntile = k0 < klim && a.Tq > qstart ? (a.Tq - qstart + 63) / 64 : 0;
+  Guide gd = {};
+  float gk = 0.f;
+  float kappa = 0.f, tkv = 0.f, g_n = 0.f;
+  const float* GR = nullptr;
+  if constexpr (G) {
+    gd = guide_of(a, b, h, klim);
+    gk = a.gk;
+    kappa = gd.sel ? *a.gcoef : 0.f;
+    tkv = (float)kv * gd.rk;
+    GR = a.grow + (int64_t)bh * a.Tq;
+  }
   uint4 rq[PER], rd[PER], ro[PER];
   // the next tile's LSE / delta are loaded with its Q / dO rows (stats_load) and stored to LDS
   // with them (stats): loaded at the store, they cost a memory round trip at every tile's end
@@ -868,6 +1035,9 @@ TT2_DEV void attn_bwd_dkdv3_body(const AttnArgs& a, int bx, int by, char* smem, 
       const int q = qb + tid;
       lse_n = q < a.Tq ? LSE[q] : INFINITY;
       if (!self_delta) dl_n = q < a.Tq ? DL[q] : 0.f;
+      if constexpr (G) {
+        if (self_delta && gd.sel) g_n = q < a.Tq ? kappa * GR[q] : 0.f;   // g is 0 on the rows past Ty
+      }
     }
   };
   auto stats = [&](int buf, int qb) {
@@ -875,6 +1045,9 @@ TT2_DEV void attn_bwd_dkdv3_body(const AttnArgs& a, int bx, int by, char* smem, 
     if (tid < 64) {
       sL[buf][tid] = lse_n;
       if (!self_delta) sDl[buf][tid] = dl_n;
+      if constexpr (G) {
+        if (self_delta && gd.sel) sG[buf][tid] = g_n;
+      }
     }
     if (self_delta) {   // chunk c = tid + NTH i is row c >> 3, 8 columns; the row's 8 chunks sit in 8 lanes
 #pragma unroll
@@ -916,6 +1089,7 @@ TT2_DEV void attn_bwd_dkdv3_body(const AttnArgs& a, int bx, int by, char* smem, 
     const bf16* cD = sdO[BUF];
     const float* cL = sL[BUF];
     const float* cDl = sDl[BUF];
+    const float* cG = sG[BUF];
 #pragma unroll
     for (int qb = 0; qb < 2; ++qb) {
       const int qb0 = q0 + 32 * qb;
@@ -939,6 +1113,13 @@ TT2_DEV void attn_bwd_dkdv3_body(const AttnArgs& a, int bx, int by, char* smem, 
           p[4 * rr + i] = fast_exp2(fmaf(s[4 * rr + i], c, -L[i]));
           dl[4 * rr + i] = Dl[i];
         }
+        if constexpr (G) {
+          if (self_delta && gd.sel) {
+            const f32x4 Gv = *reinterpret_cast<const f32x4*>(cG + qi);
+#pragma unroll
+            for (int i = 0; i < 4; ++i) dl[4 * rr + i] += Gv[i];
+          }
+        }
       }
       if (kw + 32 > klim || (a.causal && qb0 < kw + 31)) {   // wave-uniform: mask edge tiles only
         // masked: query q < kv (causal) or every query when kv >= klim
@@ -947,10 +1128,22 @@ TT2_DEV void attn_bwd_dkdv3_body(const AttnArgs& a, int bx, int by, char* smem, 
         for (int r = 0; r < 16; ++r) p[r] = crow(r, 0) < qlo ? 0.f : p[r];
       }
       bf16x8 pf[2], dsf[2];
+      if (G && gd.sel) {   // block-uniform
+        const float n0 = (float)(qb0 + 4 * hi);
+        const int nval = gd.qlim - qb0 - 4 * hi;   // query row crow is valid iff crow < nval
 #pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        pf[r >> 3][r & 7] = (bf16)p[r];
-        dsf[r >> 3][r & 7] = (bf16)(p[r] * (dp[r] - dl[r]));
+        for (int r = 0; r < 16; ++r) {
+          const float wgt = guide_w<true>(tkv, (n0 + (float)crow(r, 0)) * gd.rq, gk);
+          const float kq = crow(r, 0) < nval ? kappa : 0.f;
+          pf[r >> 3][r & 7] = (bf16)p[r];
+          dsf[r >> 3][r & 7] = (bf16)(p[r] * (fmaf(kq, wgt, dp[r]) - dl[r]));
+        }
+      } else {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          pf[r >> 3][r & 7] = (bf16)p[r];
+          dsf[r >> 3][r & 7] = (bf16)(p[r] * (dp[r] - dl[r]));
+        }
       }
 #pragma unroll
       for (int hh = 0; hh < 2; ++hh)
@@ -978,27 +1171,31 @@ TT2_DEV void attn_bwd_dkdv3_body(const AttnArgs& a, int bx, int by, char* smem, 
 }
 
 constexpr int ATTN_BWD3_SMEM = 4 * 64 * D * sizeof(bf16) + 4 * 64 * sizeof(float);   // the larger (dK / dV) body
+constexpr int ATTN_BWD3_SMEM_G = ATTN_BWD3_SMEM + 2 * 64 * sizeof(float);              // + sG (guided, self_delta)
 
-template <int NW>
-__global__ __launch_bounds__(NW * 64) void attn_bwd_dq3_kernel(AttnArgs a) {
+template <int NW, bool G>
+__global__ __launch_bounds__(NW * 64) void attn_bwd_dq3_kernel(ArgsT<G> a) {
   __shared__ __attribute__((aligned(16))) char smem[4 * 64 * D * sizeof(bf16)];
-  attn_bwd_dq3_body<NW>(a, blockIdx.x, blockIdx.y, gridDim.y, smem, true);
+  attn_bwd_dq3_body<NW, G>(a, blockIdx.x, blockIdx.y, gridDim.y, smem, true);
 }
 
-template <int NW>
-__global__ __launch_bounds__(NW * 64) void attn_bwd_dkdv3_kernel(AttnArgs a) {
-  __shared__ __attribute__((aligned(16))) char smem[ATTN_BWD3_SMEM];
-  attn_bwd_dkdv3_body<NW>(a, blockIdx.x, blockIdx.y, smem, false);
+template <int NW, bool G>
+__global__ __launch_bounds__(NW * 64) void attn_bwd_dkdv3_kernel(ArgsT<G> a) {
+  __shared__ __attribute__((aligned(16))) char smem[ATTN_BWD3_SMEM];   // (no sG: the published delta has kappa g)
+  attn_bwd_dkdv3_body<NW, G>(a, blockIdx.x, blockIdx.y, smem, false);
 }
 
 // dQ and dK / dV in one launch (each computes delta itself): y < nkb are the key blocks, the
 // rest the query blocks, so the (few, long) dK / dV workgroups of a short key range run
 // beside the dQ workgroups instead of after them on a mostly idle chip
-template <int NW>
-__global__ __launch_bounds__(NW * 64) void attn_bwd_fused3_kernel(AttnArgs a, int nkb) {
-  __shared__ __attribute__((aligned(16))) char smem[ATTN_BWD3_SMEM];
-  if ((int)blockIdx.y < nkb) attn_bwd_dkdv3_body<NW>(a, blockIdx.x, blockIdx.y, smem, true);
-  else attn_bwd_dq3_body<NW>(a, blockIdx.x, (int)blockIdx.y - nkb, (int)gridDim.y - nkb, smem, false);
+// (G: held to two waves per SIMD, the plain kernel's occupancy, without scratch; its natural
+// allocation is 260 registers.  Measured 47.3 us held against 48.7 not held)
+template <int NW, bool G>
+__global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(G ? 2 : 1)))
+void attn_bwd_fused3_kernel(ArgsT<G> a, int nkb) {
+  __shared__ __attribute__((aligned(16))) char smem[G ? ATTN_BWD3_SMEM_G : ATTN_BWD3_SMEM];
+  if ((int)blockIdx.y < nkb) attn_bwd_dkdv3_body<NW, G>(a, blockIdx.x, blockIdx.y, smem, true);
+  else attn_bwd_dq3_body<NW, G>(a, blockIdx.x, (int)blockIdx.y - nkb, (int)gridDim.y - nkb, smem, false);
 }
 
 AttnArgs to_args(const tt2_attn_args* p) {
@@ -1012,6 +1209,23 @@ AttnArgs to_args(const tt2_attn_args* p) {
   a.B = p->batch; a.H = p->heads; a.Tq = p->tq; a.Tk = p->tk; a.causal = p->causal;
   a.scale = p->scale;
   return a;
+}
+
+int attn_err(const char* who, const char* msg) {
+  return tt2_set_error(TT2_E_INVALID, (std::string(who) + ": " + msg).c_str());
+}
+
+// guided launches: non-causal only (the loss is defined on encoder-decoder attention)
+int add_guide(AttnArgsG& a, const tt2_attn_args* p, const tt2_attn_guide* g, bool bwd, const char* who) {
+  if (!g) return attn_err(who, "guide required");
+  if (p->causal) return attn_err(who, "guided attention is non-causal only");
+  if (!g->rows || (bwd && !g->coef)) return attn_err(who, "guide rows / coef required");
+  if (!(g->sigma > 0.f) || g->heads < 0 || g->heads > p->heads)
+    return attn_err(who, "guide needs sigma > 0 and 0 <= heads <= the attention's heads");
+  a.q_len = g->q_len; a.grow = g->rows; a.gcoef = g->coef;
+  a.gk = LOG2E / (2.f * g->sigma * g->sigma);
+  a.gheads = g->heads;
+  return TT2_OK;
 }
 
 int validate(const tt2_attn_args* p) {
@@ -1080,30 +1294,46 @@ extern "C" int tt2_attn_probs(const tt2_attn_args* p, float* probs, hipStream_t 
   return tt2_check_launch(hipGetLastError(), "tt2_attn_probs");
 }
 
-extern "C" int tt2_attn_fwd(const tt2_attn_args* p, hipStream_t s) {
+template <bool G>
+static int attn_fwd_launch(const tt2_attn_args* p, const tt2_attn_guide* g, hipStream_t s, const char* who) {
   if (int rc = validate(p)) return rc;
-  if (!p->o_out || !p->lse) return tt2_set_error(TT2_E_INVALID, "tt2_attn_fwd: out/lse required");
+  if (!p->o_out || !p->lse) return attn_err(who, "out/lse required");
+  ArgsT<G> a;
+  static_cast<AttnArgs&>(a) = to_args(p);
+  if constexpr (G)
+    if (int rc = add_guide(a, p, g, false, who)) return rc;
   if (p->batch * p->tq == 0) return TT2_OK;
-  AttnArgs a = to_args(p);
   const int nw = v3_waves(p, p->tq, true);
   if (nw == 4) {
-    hipLaunchKernelGGL(attn_fwd3_kernel<4>, dim3(p->batch * p->heads, (p->tq + 127) / 128), dim3(256), 0, s, a);
+    hipLaunchKernelGGL((attn_fwd3_kernel<4, G>), dim3(p->batch * p->heads, (p->tq + 127) / 128), dim3(256), 0, s, a);
   } else if (nw == 2) {
-    hipLaunchKernelGGL(attn_fwd3_kernel<2>, dim3(p->batch * p->heads, (p->tq + 63) / 64), dim3(128), 0, s, a);
+    hipLaunchKernelGGL((attn_fwd3_kernel<2, G>), dim3(p->batch * p->heads, (p->tq + 63) / 64), dim3(128), 0, s, a);
   } else {
     dim3 grid((p->tq + BQ - 1) / BQ, p->batch * p->heads);
-    if (p->dtype == TT2_DT_BF16) hipLaunchKernelGGL(attn_fwd_kernel<bf16>, grid, dim3(NT), 0, s, a);
-    else hipLaunchKernelGGL(attn_fwd_kernel<float>, grid, dim3(NT), 0, s, a);
+    if (p->dtype == TT2_DT_BF16) hipLaunchKernelGGL((attn_fwd_kernel<bf16, G>), grid, dim3(NT), 0, s, a);
+    else hipLaunchKernelGGL((attn_fwd_kernel<float, G>), grid, dim3(NT), 0, s, a);
   }
-  return tt2_check_launch(hipGetLastError(), "tt2_attn_fwd");
+  return tt2_check_launch(hipGetLastError(), who);
 }
 
-extern "C" int tt2_attn_bwd(const tt2_attn_args* p, hipStream_t s) {
+extern "C" int tt2_attn_fwd(const tt2_attn_args* p, hipStream_t s) {
+  return attn_fwd_launch<false>(p, nullptr, s, "tt2_attn_fwd");
+}
+
+extern "C" int tt2_attn_fwd_guided(const tt2_attn_args* p, const tt2_attn_guide* g, hipStream_t s) {
+  return attn_fwd_launch<true>(p, g, s, "tt2_attn_fwd_guided");
+}
+
+template <bool G>
+static int attn_bwd_launch(const tt2_attn_args* p, const tt2_attn_guide* g, hipStream_t s, const char* who) {
   if (int rc = validate(p)) return rc;
   if (!p->dq || !p->dk || !p->dv || !p->delta || !p->lse || !p->o || !p->dout)
-    return tt2_set_error(TT2_E_INVALID, "tt2_attn_bwd: missing buffer");
+    return attn_err(who, "missing buffer");
+  ArgsT<G> a;
+  static_cast<AttnArgs&>(a) = to_args(p);
+  if constexpr (G)
+    if (int rc = add_guide(a, p, g, true, who)) return rc;
   if (p->batch * p->tq == 0) return TT2_OK;
-  AttnArgs a = to_args(p);
   const int BH = p->batch * p->heads;
   dim3 gprep((p->batch * p->tq + 3) / 4);
   if (p->dtype == TT2_DT_BF16) {
@@ -1115,23 +1345,99 @@ extern "C" int tt2_attn_bwd(const tt2_attn_args* p, hipStream_t s) {
       // parts: both halves (the dK / dV blocks compute delta themselves, the dQ blocks do not
       // publish it), or one of them alone
       const int nkb = p->parts == 1 ? 0 : (p->tk + 127) / 128, nqb = p->parts == 2 ? 0 : (p->tq + 127) / 128;
-      hipLaunchKernelGGL(attn_bwd_fused3_kernel<4>, dim3(BH, nkb + nqb), dim3(256), 0, s, a, nkb);
-      return tt2_check_launch(hipGetLastError(), "tt2_attn_bwd");
+      hipLaunchKernelGGL((attn_bwd_fused3_kernel<4, G>), dim3(BH, nkb + nqb), dim3(256), 0, s, a, nkb);
+      return tt2_check_launch(hipGetLastError(), who);
     }
     if (p->parts != 0)
-      return tt2_set_error(TT2_E_INVALID, "tt2_attn_bwd: parts needs the non-causal bf16 launch (4-wave v3)");
-    if (nq == 0) hipLaunchKernelGGL(attn_bwd_prep_kernel<bf16>, gprep, dim3(NT), 0, s, a);
-    if (nq == 4) hipLaunchKernelGGL(attn_bwd_dq3_kernel<4>, dim3(BH, (p->tq + 127) / 128), dim3(256), 0, s, a);
-    else if (nq == 2) hipLaunchKernelGGL(attn_bwd_dq3_kernel<2>, dim3(BH, (p->tq + 63) / 64), dim3(128), 0, s, a);
-    else hipLaunchKernelGGL(attn_bwd_dq_kernel<bf16>, dim3((p->tq + BQ - 1) / BQ, BH), dim3(NT), 0, s, a);
-    if (nk == 4) hipLaunchKernelGGL(attn_bwd_dkdv3_kernel<4>, dim3(BH, (p->tk + 127) / 128), dim3(256), 0, s, a);
-    else if (nk == 2) hipLaunchKernelGGL(attn_bwd_dkdv3_kernel<2>, dim3(BH, (p->tk + 63) / 64), dim3(128), 0, s, a);
-    else hipLaunchKernelGGL(attn_bwd_dkdv_kernel<bf16>, dim3((p->tk + BKV - 1) / BKV, BH), dim3(NT), 0, s, a);
+      return attn_err(who, "parts needs the non-causal bf16 launch (4-wave v3)");
+    if (nq == 0) hipLaunchKernelGGL((attn_bwd_prep_kernel<bf16, G>), gprep, dim3(NT), 0, s, a);
+    if (nq == 4) hipLaunchKernelGGL((attn_bwd_dq3_kernel<4, G>), dim3(BH, (p->tq + 127) / 128), dim3(256), 0, s, a);
+    else if (nq == 2) hipLaunchKernelGGL((attn_bwd_dq3_kernel<2, G>), dim3(BH, (p->tq + 63) / 64), dim3(128), 0, s, a);
+    else hipLaunchKernelGGL((attn_bwd_dq_kernel<bf16, G>), dim3((p->tq + BQ - 1) / BQ, BH), dim3(NT), 0, s, a);
+    if (nk == 4) hipLaunchKernelGGL((attn_bwd_dkdv3_kernel<4, G>), dim3(BH, (p->tk + 127) / 128), dim3(256), 0, s, a);
+    else if (nk == 2) hipLaunchKernelGGL((attn_bwd_dkdv3_kernel<2, G>), dim3(BH, (p->tk + 63) / 64), dim3(128), 0, s, a);
+    else hipLaunchKernelGGL((attn_bwd_dkdv_kernel<bf16, G>), dim3((p->tk + BKV - 1) / BKV, BH), dim3(NT), 0, s, a);
   } else {
-    if (p->parts != 0) return tt2_set_error(TT2_E_INVALID, "tt2_attn_bwd: parts needs bf16");
-    hipLaunchKernelGGL(attn_bwd_prep_kernel<float>, gprep, dim3(NT), 0, s, a);
-    hipLaunchKernelGGL(attn_bwd_dq_kernel<float>, dim3((p->tq + BQ - 1) / BQ, BH), dim3(NT), 0, s, a);
-    hipLaunchKernelGGL(attn_bwd_dkdv_kernel<float>, dim3((p->tk + BKV - 1) / BKV, BH), dim3(NT), 0, s, a);
+    if (p->parts != 0) return attn_err(who, "parts needs bf16");
+    hipLaunchKernelGGL((attn_bwd_prep_kernel<float, G>), gprep, dim3(NT), 0, s, a);
+    hipLaunchKernelGGL((attn_bwd_dq_kernel<float, G>), dim3((p->tq + BQ - 1) / BQ, BH), dim3(NT), 0, s, a);
+    hipLaunchKernelGGL((attn_bwd_dkdv_kernel<float, G>), dim3((p->tk + BKV - 1) / BKV, BH), dim3(NT), 0, s, a);
   }
-  return tt2_check_launch(hipGetLastError(), "tt2_attn_bwd");
+  return tt2_check_launch(hipGetLastError(), who);
+}
+
+extern "C" int tt2_attn_bwd(const tt2_attn_args* p, hipStream_t s) {
+  return attn_bwd_launch<false>(p, nullptr, s, "tt2_attn_bwd");
+}
+
+extern "C" int tt2_attn_bwd_guided(const tt2_attn_args* p, const tt2_attn_guide* g, hipStream_t s) {
+  return attn_bwd_launch<true>(p, g, s, "tt2_attn_bwd_guided");
+}
+
+// ---------------------------------------------------------- guided-attention loss
+// One work group, fixed order (no atomics): sum of the selected layers' g rows over the guided
+// heads, N = layers * heads * sum_b Tx_b Ty_b from the device lengths, the loss term, and kappa
+// for the backward.  Rows past Ty_b and empty rows hold exactly 0, so whole rows are summed.
+namespace {
+constexpr int GL_NT = 1024;
+
+template <int VEC>
+__global__ __launch_bounds__(GL_NT) void guide_loss_kernel(tt2_guide_loss_args a) {
+  __shared__ float red[GL_NT];
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int per = a.guide_heads * a.tq / VEC;   // guided heads of one batch element: contiguous
+  const int64_t bstride = (int64_t)a.heads * a.tq;
+  const int npair = a.n_layers * a.batch;
+  float acc = 0.f;
+  // wave w takes the (layer, batch) pairs w, w + 16, ...; its lanes stride the pair's rows
+  for (int pr = w; pr < npair; pr += GL_NT / 64) {
+    const int l = pr / a.batch, b = pr - l * a.batch;
+    const float* src = a.rows[l] + b * bstride;
+#pragma unroll 8
+    for (int i = lane; i < per; i += 64) {
+      if constexpr (VEC == 4) {
+        const f32x4 v = *reinterpret_cast<const f32x4*>(src + 4 * i);
+        acc += (v[0] + v[1]) + (v[2] + v[3]);
+      } else {
+        acc += src[i];
+      }
+    }
+  }
+  red[tid] = acc;
+  __syncthreads();
+  for (int st = GL_NT / 2; st > 0; st >>= 1) {
+    if (tid < st) red[tid] += red[tid + st];
+    __syncthreads();
+  }
+  if (tid == 0) {
+    double n = 0.0;
+    for (int b = 0; b < a.batch; ++b) {
+      int kl = a.tk, ql = a.tq;
+      if (a.key_len) kl = min(kl, a.key_len[b]);
+      if (a.q_len) ql = min(ql, a.q_len[b]);
+      n += (double)max(kl, 0) * (double)max(ql, 0);
+    }
+    n *= (double)a.n_layers * (double)a.guide_heads;
+    const float term = n > 0.0 ? (float)((double)a.scale * (double)red[0] / n) : 0.f;
+    *a.term = term;
+    *a.coef = n > 0.0 ? (float)((double)a.scale * (double)a.grad_scale / n) : 0.f;
+    if (a.loss_out && n > 0.0) a.loss_out[0] += term;
+  }
+}
+}  // namespace
+
+extern "C" int tt2_guided_attn_loss(const tt2_guide_loss_args* p, hipStream_t s) {
+  const char* who = "tt2_guided_attn_loss";
+  if (!p || !p->term || !p->coef) return attn_err(who, "term / coef required");
+  if (p->n_layers < 0 || p->n_layers > TT2_GUIDE_MAX_LAYERS) return attn_err(who, "too many layers");
+  if (p->batch < 0 || p->tq < 0 || p->tk < 0 || p->heads <= 0 || p->guide_heads < 0 || p->guide_heads > p->heads ||
+      (int64_t)p->heads * p->tq > INT32_MAX)
+    return attn_err(who, "shape");
+  for (int l = 0; l < p->n_layers; ++l)
+    if (!p->rows[l]) return attn_err(who, "rows buffer missing");
+  bool vec = ((int64_t)p->guide_heads * p->tq) % 4 == 0 && ((int64_t)p->heads * p->tq) % 4 == 0;
+  for (int l = 0; l < p->n_layers; ++l) vec = vec && reinterpret_cast<uintptr_t>(p->rows[l]) % 16 == 0;
+  if (vec) hipLaunchKernelGGL(guide_loss_kernel<4>, dim3(1), dim3(GL_NT), 0, s, *p);
+  else hipLaunchKernelGGL(guide_loss_kernel<1>, dim3(1), dim3(GL_NT), 0, s, *p);
+  return tt2_check_launch(hipGetLastError(), who);
 }

@@ -159,6 +159,30 @@ SIGNATURES.update({
 })
 
 
+class AttnGuide(C.Structure):
+    """tt2_attn_guide: the guided-attention side of a non-causal attention launch."""
+    _fields_ = [("q_len", vp), ("rows", vp), ("coef", vp), ("sigma", f32), ("heads", i32)]
+
+
+GUIDE_MAX_LAYERS = 16   # TT2_GUIDE_MAX_LAYERS
+
+
+class GuideLossArgs(C.Structure):
+    _fields_ = [
+        ("rows", vp * GUIDE_MAX_LAYERS), ("key_len", vp), ("q_len", vp),
+        ("loss_out", vp), ("term", vp), ("coef", vp),
+        ("n_layers", i32), ("batch", i32), ("heads", i32), ("guide_heads", i32), ("tq", i32), ("tk", i32),
+        ("scale", f32), ("grad_scale", f32),
+    ]
+
+
+SIGNATURES.update({
+    "tt2_attn_fwd_guided": ([C.POINTER(AttnArgs), C.POINTER(AttnGuide), vp], C.c_int),
+    "tt2_attn_bwd_guided": ([C.POINTER(AttnArgs), C.POINTER(AttnGuide), vp], C.c_int),
+    "tt2_guided_attn_loss": ([C.POINTER(GuideLossArgs), vp], C.c_int),
+})
+
+
 class ReduceArgs(C.Structure):
     _fields_ = [("src", vp), ("dst", vp), ("ld", i64), ("rows", i32), ("cols", i32), ("beta", f32)]
 

@@ -20,7 +20,7 @@ import os
 import torch
 
 from . import ops
-from ._lib import ACT_NONE, ACT_RELU, ACT_TANH
+from ._lib import ACT_NONE, ACT_RELU, ACT_TANH, GUIDE_MAX_LAYERS
 from .trace import ranged
 from .config import (SITE_DEC_FC1, SITE_DEC_FC2, SITE_DEC_LAYER, SITE_DEC_PE, SITE_ENC_CONV, SITE_ENC_LAYER,
                      SITE_ENC_PE, SITE_POSTNET, TTSConfig)
@@ -268,6 +268,10 @@ class TTSEngine:
         # consumed by the deferred Adam or by flush_optimizer), so a captured step never applies
         # an update twice after an eager flush, nor a stale one after load_state_dict
         self.pipeline_opt = False
+        # guided-attention loss (opt-in: TransformerTTS.guided_attention): dict(sigma, scale, heads,
+        # layers) or None.  On, the selected decoder layers' cross-attention takes the guided
+        # kernels (g rows per layer in the arena) and loss() adds the term (see set_guide)
+        self.guide = None
         self._adam_parts = None   # the clip-norm partials the deferred Adam reads (a fixed buffer)
         self.cd = dtype
         self.dev = torch.device(device)
@@ -346,7 +350,54 @@ class TTSEngine:
         key = (B, Tx, Ty)
         if key not in self.arenas:
             self.arenas[key] = Arena(self.cfg, B, Tx, Ty, self.cd, self.dev)
+            self._guide_specs(self.arenas[key])
         return self.arenas[key]
+
+    # ------------------------------------------------------------ guided attention
+    def set_guide(self, sigma=0.4, scale=10.0, heads=2, layers=None, on=True):
+        """Diagonal guided-attention loss on the first `heads` heads of the decoder layers
+        `layers` (default all): L = scale * mean over valid (layer, head, frame, phoneme) of
+        P * W, W = 1 - exp(-(t / Tx - n / Ty)^2 / (2 sigma^2)).  Off: every launch as without it."""
+        if not on:
+            self.guide = None
+            return
+        c = self.cfg
+        layers = tuple(range(c.n_dec)) if layers is None else tuple(sorted({int(l) % c.n_dec for l in layers}))
+        if not sigma > 0:
+            raise ValueError("guided_attention: sigma must be positive")
+        if not 0 <= heads <= c.n_heads:
+            raise ValueError(f"guided_attention: heads must be in 0..{c.n_heads}")
+        if len(layers) > GUIDE_MAX_LAYERS:
+            raise ValueError(f"guided_attention: at most {GUIDE_MAX_LAYERS} layers")
+        self.guide = dict(sigma=float(sigma), scale=float(scale), heads=int(heads), layers=layers)
+        for A in self.arenas.values():
+            self._guide_specs(A)
+
+    def _guide_specs(self, A: "Arena"):
+        """The guided layers' g rows, the term and kappa: arena buffers that exist only once
+        guidance has been switched on (allocated on first use, or by materialize())."""
+        if self.guide is None:
+            return
+        f32 = torch.float32
+        for l in self.guide["layers"]:
+            A.spec.setdefault(f"garow{l}", ((A.B * self.cfg.n_heads, A.Ty), f32, True))
+        A.spec.setdefault("ga_term", ((1,), f32, True))
+        A.spec.setdefault("ga_coef", ((1,), f32, True))
+
+    def _guide_kw(self, A: "Arena", l: int):
+        """Keyword arguments of ops.attn_{fwd,bwd}_guided for decoder layer l, or None."""
+        g = self.guide
+        if g is None or l not in g["layers"]:
+            return None
+        return dict(rows=A[f"garow{l}"], q_len=A["mel_len"], sigma=g["sigma"], guide_heads=g["heads"])
+
+    def guide_loss(self, A: "Arena", grad_scale: float, loss_out=None):
+        """The guided term of the last forward into A["ga_term"], kappa = scale * grad_scale / N
+        into A["ga_coef"] (the guided backward reads it), and the term added to loss_out[0]."""
+        g = self.guide
+        ops.guided_attn_loss([A[f"garow{l}"] for l in g["layers"]], A["ga_term"], A["ga_coef"], A.B,
+                             self.cfg.n_heads, A.Ty, A.Tx, key_len=A["text_len"], q_len=A["mel_len"],
+                             guide_heads=g["heads"], scale=g["scale"], grad_scale=grad_scale, loss_out=loss_out)
 
     # ------------------------------------------------------------ GEMM helpers
     def _lin(self, x, w, out, m, n, k, bias=None, act=ACT_NONE, drop=NO_DROP, res=None, ldx=None, ldo=None,
@@ -817,8 +868,13 @@ class TTSEngine:
             ko = 2 * d * l
             if l <= 1:
                 yield
-            ops.attn_fwd(A[f"dcq{l}"], mkv[:, ko:], mkv[:, ko + d:], A[f"dcatt{l}"], A[f"dclse{l}"], d, kvld, kvld,
-                         d, B, H, Ty, Tx, A["text_len"], False, scale)
+            gkw = self._guide_kw(A, l)
+            if gkw is not None:
+                ops.attn_fwd_guided(A[f"dcq{l}"], mkv[:, ko:], mkv[:, ko + d:], A[f"dcatt{l}"], A[f"dclse{l}"],
+                                    gkw.pop("rows"), d, kvld, kvld, d, B, H, Ty, Tx, A["text_len"], scale=scale, **gkw)
+            else:
+                ops.attn_fwd(A[f"dcq{l}"], mkv[:, ko:], mkv[:, ko + d:], A[f"dcatt{l}"], A[f"dclse{l}"], d, kvld,
+                             kvld, d, B, H, Ty, Tx, A["text_len"], False, scale)
             self._lin(A[f"dcatt{l}"], self.W(p + "co.w"), A[f"dco{l}"], Md, d, d, bias=self.P(p + "co.b"))
             ops.layernorm_fwd(h1, A[f"dco{l}"], self.P(p + "ln2.g"), self.P(p + "ln2.b"), A[f"dh2{l}"],
                               A[f"dln2m{l}"], A[f"dln2r{l}"], Md, c.ln_eps, drop=self.drop(base + 1, c.dropout))
@@ -875,6 +931,8 @@ class TTSEngine:
         c = self.cfg
         ops.tts_loss(A["heads"], A.heads_ld, A["mel_after"], A["mel"], A["mel_len"], A["loss"], A["g_heads"],
                      A["g_after"], A.B, A.Ty, c.n_mels, c.stop_pos_weight, self.grad_scale, ws=self.ws)
+        if self.guide is not None:
+            self.guide_loss(A, self.grad_scale, loss_out=A["loss"])
 
     # ------------------------------------------------------------ backward
     def ready_names(self) -> list[str]:
@@ -1022,7 +1080,12 @@ class TTSEngine:
             xargs = (A[f"dcq{l}"], mkv[:, ko:], mkv[:, ko + d:], A[f"dcatt{l}"], A["g_att"], A[f"dclse{l}"],
                      A["delta"], g_cq, g_mkv[:, ko:], g_mkv[:, ko + d:], d, kvld, kvld, d, d, d, kvld, kvld,
                      B, H, Ty, Tx, A["text_len"], False, scale)
-            ops.attn_bwd(*xargs)
+            gkw = self._guide_kw(A, l)
+            if gkw is not None:
+                ops.attn_bwd_guided(*xargs[:10], gkw.pop("rows"), A["ga_coef"], *xargs[10:22], key_len=xargs[22],
+                                    scale=xargs[24], **gkw)
+            else:
+                ops.attn_bwd(*xargs)
             self._wgrad(g_cq, h1, self.G(p + "cq.w"), d, d, Md, gb=self.G(p + "cq.b"))
             self._dgrad(g_cq, self.W(p + "cq.w"), gx2, Md, d, d, res=A["g_res"])
             gx, gx2 = gx2, gx

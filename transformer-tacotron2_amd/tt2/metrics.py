@@ -46,7 +46,7 @@ def step_flops(cfg, B: int, Tx: int, Ty: int) -> float:
 class StepMetrics:
     """Appends one JSON line per step to `path` (see the module docstring)."""
 
-    LOSS_KEYS = ("total", "mse_before", "mse_after", "bce_stop")
+    LOSS_KEYS = ("total", "mse_before", "mse_after", "bce_stop", "guided_attn")   # the last with guidance only
 
     def __init__(self, path: str, cfg, world: int | None = None):
         """world: ranks whose frames count in frames/s; None: torch.distributed's world size,
@@ -71,9 +71,14 @@ class StepMetrics:
             self.world = dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
         return self.world
 
-    def end(self, loss: torch.Tensor, B: int, Tx: int, Ty: int, sync=None, mel_len: torch.Tensor | None = None):
+    def end(self, loss: torch.Tensor, B: int, Tx: int, Ty: int, sync=None, mel_len: torch.Tensor | None = None,
+            guided: torch.Tensor | None = None):
+        """guided: the step's guided-attention term (device scalar), when guidance is on: the
+        line's loss then also has "guided_attn" (already part of "total")."""
         ev = torch.cuda.Event(enable_timing=True)
         ev.record()
+        if guided is not None:
+            loss = torch.cat([loss.detach().reshape(-1), guided.detach().reshape(-1)])
         ar = sync.pop_span() if sync is not None and hasattr(sync, "pop_span") else None
         valid = mel_len.detach().to(torch.int64).sum() if mel_len is not None else None   # device scalar, no sync
         cur = (self._open, ev, loss.detach().clone(), (B, Tx, Ty), ar, time.time(), valid)

@@ -50,17 +50,30 @@ class _TTSForward(torch.autograd.Function):
     def forward(ctx, model, text, text_len, mel, mel_len, *params):
         A = model._run_forward(text, text_len, mel, mel_len)
         ctx.model, ctx.A, ctx.gen = model, A, A.gen
-        return model.outputs(A)[:3]
+        out = model.outputs(A)
+        ctx.guided = out[3] is not None
+        if ctx.guided:   # the guided-attention term is the fourth (differentiable) output
+            ctx.kappa = A["ga_coef"].clone()   # scale / N; backward scales it by the incoming gradient
+            return out
+        return out[:3]
 
     @staticmethod
     @once_differentiable
-    def backward(ctx, g_before, g_after, g_stop):
+    def backward(ctx, g_before, g_after, g_stop, g_guided=None):
         model, A = ctx.model, ctx.A
         if A.gen != ctx.gen:
             raise RuntimeError("TransformerTTS: another forward of the same (B, Tx, Ty) shape overwrote the "
                                "activations this backward needs; call backward before the next forward")
         model._stage_output_grads(A, g_before, g_after, g_stop)
         e = model.engine
+        if ctx.guided:
+            if e.guide is None:
+                raise RuntimeError("TransformerTTS: guided attention was switched off between this forward "
+                                   "and its backward")
+            if g_guided is None:
+                A["ga_coef"].zero_()
+            else:   # kappa * d(total)/d(term), on the device
+                torch.mul(ctx.kappa, g_guided.reshape(1).to(ctx.kappa.dtype), out=A["ga_coef"])
         e.backward(A)
         if e.training:   # fresh dropout masks for the next step (the fused path bumps in its optimizer)
             ops.step_bump(model._seed_steps, e.seed)
@@ -107,6 +120,7 @@ class TransformerTTS(nn.Module):
         self._slot_names = [key2slot[k] for k in self.slots.keys()]
         self._shadow_version = e.params._version
         self._seed_steps = torch.zeros(1, dtype=torch.int32, device=e.dev)
+        self._guide_epoch = 0   # bumped by guided_attention(): captured steps from before it refuse to run
 
     def _apply(self, fn, recurse=True):
         raise NotImplementedError("TransformerTTS parameters live in libtt2's flat buffers: choose device and "
@@ -143,6 +157,21 @@ class TransformerTTS(nn.Module):
         if not on:
             self.engine.flush_optimizer()
         self.engine.pipeline_opt = on
+
+    def guided_attention(self, sigma: float = 0.4, scale: float = 10.0, heads: int = 2, layers=None,
+                         on: bool = True):
+        """Diagonal guided-attention loss (opt-in; SpeechT5 / ESPnet convention) on the first
+        `heads` heads of the decoder layers `layers` (default: all) of the encoder-decoder
+        attention:  L_ga = scale * mean over valid (layer, head, frame n, phoneme t) of
+        P[n, t] * (1 - exp(-(t / Tx_b - n / Ty_b)^2 / (2 sigma^2))).  It is computed inside the
+        cross-attention kernels (no attention matrix is stored) and joins the training loss:
+        train_step / loss() include it in the total and report it as parts["guided_attn"];
+        forward() returns it as its fourth output, which loss(outputs, ...) adds.  Not a config
+        field: checkpoints are unchanged.  A step captured before the switch changed must be
+        captured again (its run() raises).  on=False: every launch as without it."""
+        self.engine.set_guide(sigma=sigma, scale=scale, heads=heads, layers=layers, on=on)
+        self._graphs.clear()
+        self._guide_epoch += 1
 
     def flush_optimizer(self):
         """Run a pipelined step's pending Adam now."""
@@ -247,13 +276,14 @@ class TransformerTTS(nn.Module):
 
     def forward(self, text, text_len, mel, mel_len):
         """Teacher-forced forward (shift-right with a zero go frame).  Returns
-        (mel_before [B,Ty,80], mel_after [B,Ty,80], stop_logits [B,Ty], None), f32.
+        (mel_before [B,Ty,80], mel_after [B,Ty,80], stop_logits [B,Ty], None), f32; with
+        guided_attention() on, the fourth output is the guided-attention term (a scalar).
         With grad mode on, the outputs carry an autograd node whose backward runs the
         engine's backward (so loss.backward() fills every parameter's .grad)."""
         params = list(self.slots.values())
         if torch.is_grad_enabled() and any(p.requires_grad for p in params):
-            mb, ma, st = _TTSForward.apply(self, text, text_len, mel, mel_len, *params)
-            return mb, ma, st, None
+            out = _TTSForward.apply(self, text, text_len, mel, mel_len, *params)
+            return tuple(out) if len(out) == 4 else (*out, None)
         return self.outputs(self._run_forward(text, text_len, mel, mel_len))
 
     def _stage_output_grads(self, A: Arena, g_before, g_after, g_stop):
@@ -302,21 +332,31 @@ class TransformerTTS(nn.Module):
         mel_before = heads[:, :c.n_mels].reshape(B, Ty, c.n_mels).clone()
         stop = heads[:, c.n_mels].reshape(B, Ty).clone()
         mel_after = A["mel_after"].view(B, Ty, c.n_mels).clone()
-        return mel_before, mel_after, stop, None
+        guided = None
+        if self.engine.guide is not None:   # term and kappa (= scale / N) of this forward
+            self.engine.guide_loss(A, 1.0)
+            guided = A["ga_term"][0].clone()
+        return mel_before, mel_after, stop, guided
 
     def loss(self, outputs=None, mel=None, mel_len=None):
         """loss(outputs, mel, mel_len): the TTS loss of the given outputs (mel_before,
         mel_after, stop_logits, ...) against mel / mel_len, differentiable w.r.t. the outputs.
         loss() with no outputs: the engine fast path -- the loss of the last forward against
         the mel it was given (or mel / mel_len if passed), feeding backward().
-        Returns (total, {"mel_before", "mel_after", "stop"}) as device scalars."""
+        Returns (total, {"mel_before", "mel_after", "stop"}) as device scalars; with
+        guided_attention() on, the total includes the guided term (outputs[3], when outputs are
+        given) and the parts have it as "guided_attn"."""
         if outputs is not None:
             if mel is None or mel_len is None:
                 raise ValueError("loss(outputs, mel, mel_len): mel and mel_len are required with outputs")
             dev = self.engine.dev
             total, lb, la, ls = _TTSLoss.apply(self, outputs[0], outputs[1], outputs[2],
                                                mel.to(dev, torch.float32), mel_len.to(dev, torch.int32))
-            return total, {"mel_before": lb, "mel_after": la, "stop": ls}
+            parts = {"mel_before": lb, "mel_after": la, "stop": ls}
+            if len(outputs) > 3 and outputs[3] is not None:
+                total = total + outputs[3]
+                parts["guided_attn"] = outputs[3].detach()
+            return total, parts
         A = self._last
         if A is None:
             raise RuntimeError("loss() needs a forward() first")
@@ -326,7 +366,10 @@ class TransformerTTS(nn.Module):
             A["mel_len"].copy_(mel_len)
         self.engine.loss(A)
         L = A["loss"]
-        return L[0], {"mel_before": L[1], "mel_after": L[2], "stop": L[3]}
+        parts = {"mel_before": L[1], "mel_after": L[2], "stop": L[3]}
+        if self.engine.guide is not None:
+            parts["guided_attn"] = A["ga_term"][0]
+        return L[0], parts
 
     def backward(self):
         if self._last is None:
@@ -406,7 +449,8 @@ class TransformerTTS(nn.Module):
             self.metrics = StepMetrics(path, self.cfg, world)
 
     def _metrics_end(self, A: Arena, sync_grads):
-        self.metrics.end(A["loss"], A.B, A.Tx, A.Ty, sync=getattr(sync_grads, "__self__", None), mel_len=A["mel_len"])
+        self.metrics.end(A["loss"], A.B, A.Tx, A.Ty, sync=getattr(sync_grads, "__self__", None), mel_len=A["mel_len"],
+                         guided=A["ga_term"] if self.engine.guide is not None else None)
 
     def train_step(self, text, text_len, mel, mel_len, sync_grads=None):
         """One optimisation step, eagerly.  Returns the device loss vector
@@ -438,6 +482,7 @@ class TransformerTTS(nn.Module):
             raise RuntimeError("capture_train_step: with the pipelined optimizer, capture after an eager step "
                                "(the graph holds that step's deferred Adam)")
         A = e.arena(B, Tx, Ty)
+        epoch = self._guide_epoch
         # the caller's warm-up eager steps size every workspace; capture must not allocate.
         # Every arena buffer exists before capture (the warm-ups may have run the overlapped
         # backward, which uses per-layer copies in place of some shared scratch buffers)
@@ -516,6 +561,7 @@ class TransformerTTS(nn.Module):
         self._graphs[(B, Tx, Ty)] = (segs, g2)
 
         def run(text, text_len, mel, mel_len):
+            self._check_capture(epoch)
             if self.metrics is not None:
                 self.metrics.begin()
             self._stage_into(A, text, text_len, mel, mel_len)
@@ -535,6 +581,11 @@ class TransformerTTS(nn.Module):
 
         return run
 
+    def _check_capture(self, epoch: int):
+        if epoch != self._guide_epoch:
+            raise RuntimeError("TransformerTTS: guided_attention() changed after this step was captured; "
+                               "call capture_train_step again")
+
     def _capture_streams(self, sync=None) -> dict:
         """The streams a captured step may fork into the capture, by role."""
         e = self.engine
@@ -551,6 +602,7 @@ class TransformerTTS(nn.Module):
         fork onto the comm stream inside the capture as each bucket's gradients become
         final, overlap the rest of the backward, and join before Adam."""
         e = self.engine
+        epoch = self._guide_epoch
         g = torch.cuda.CUDAGraph()
         s = torch.cuda.Stream()
         s.wait_stream(torch.cuda.current_stream())
@@ -578,6 +630,7 @@ class TransformerTTS(nn.Module):
         self._graphs[(A.B, A.Tx, A.Ty)] = ([(g, [])], None)
 
         def run(text, text_len, mel, mel_len):
+            self._check_capture(epoch)
             if self.metrics is not None:
                 self.metrics.begin()
             self._stage_into(A, text, text_len, mel, mel_len)
@@ -586,7 +639,8 @@ class TransformerTTS(nn.Module):
                 e.nbt[k] += 1
             self._last = A
             if self.metrics is not None:
-                self.metrics.end(A["loss"], A.B, A.Tx, A.Ty, mel_len=A["mel_len"])   # all-reduce span: inside the graph
+                self.metrics.end(A["loss"], A.B, A.Tx, A.Ty, mel_len=A["mel_len"],   # all-reduce span: inside the graph
+                                 guided=A["ga_term"] if e.guide is not None else None)
             return A["loss"]
 
         return run

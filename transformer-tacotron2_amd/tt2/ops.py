@@ -341,6 +341,103 @@ def attn_bwd(q, k, v, o, dout, lse, delta, dq, dk, dv, q_ld, k_ld, v_ld, o_ld, d
     check(L.tt2_attn_bwd(C.byref(a), stream_ptr()), "tt2_attn_bwd")
 
 
+def _need(what, t, numel, dtype):
+    if t.dtype != dtype or t.numel() < numel:
+        raise _lib.TT2Error(f"{what}: needs {numel} elements of {dtype}, got {t.numel()} of {t.dtype}")
+
+
+def _span(ld, rows, cols=64):
+    """Elements a [rows, >= cols] tensor (or column-slice view of row stride ld) holds at least."""
+    if rows > 0 and ld < cols:
+        raise _lib.TT2Error(f"attn: leading dimension {ld} below the {cols} head columns")
+    return rows * cols
+
+
+def _attn_guide(what, rows, q_len, coef, sigma, guide_heads, batch, heads, tq):
+    g = _lib.AttnGuide()
+    _need(f"{what}: rows", rows, batch * heads * tq, torch.float32)
+    if q_len is not None:
+        _need(f"{what}: q_len", q_len, batch, torch.int32)
+    if coef is not None:
+        _need(f"{what}: coef", coef, 1, torch.float32)
+    g.q_len, g.rows, g.coef, g.sigma, g.heads = ptr(q_len), rows.data_ptr(), ptr(coef), sigma, guide_heads
+    return g
+
+
+def attn_fwd_guided(q, k, v, out, lse, rows, q_ld, k_ld, v_ld, o_ld, batch, heads, tq, tk, key_len=None,
+                    q_len=None, sigma=0.4, guide_heads=2, causal=False, scale=0.125):
+    """attn_fwd that also stores g[n] = sum_t P[n, t] W[n, t] of the guided heads (h < guide_heads)
+    into rows [batch*heads, tq] f32 (tt2_attn_guide); out and lse are attn_fwd's bit for bit."""
+    L = lib()
+    a = _attn_common(q, k, v, q_ld, k_ld, v_ld, batch, heads, tq, tk, key_len, causal, scale)
+    hd = heads * 64
+    cd = q.dtype
+    _need("attn_fwd_guided: q", q, _span(q_ld, batch * tq, hd), cd)
+    _need("attn_fwd_guided: k", k, _span(k_ld, batch * tk, hd), cd)
+    _need("attn_fwd_guided: v", v, _span(v_ld, batch * tk, hd), cd)
+    _need("attn_fwd_guided: out", out, _span(o_ld, batch * tq, hd), cd)
+    _need("attn_fwd_guided: lse", lse, batch * heads * tq, torch.float32)
+    if key_len is not None:
+        _need("attn_fwd_guided: key_len", key_len, batch, torch.int32)
+    g = _attn_guide("attn_fwd_guided", rows, q_len, None, sigma, guide_heads, batch, heads, tq)
+    a.o_out, a.o_ld, a.lse = out.data_ptr(), o_ld, lse.data_ptr()
+    check(L.tt2_attn_fwd_guided(C.byref(a), C.byref(g), stream_ptr()), "tt2_attn_fwd_guided")
+    return out
+
+
+def attn_bwd_guided(q, k, v, o, dout, lse, delta, dq, dk, dv, rows, coef, q_ld, k_ld, v_ld, o_ld, do_ld, dq_ld,
+                    dk_ld, dv_ld, batch, heads, tq, tk, key_len=None, q_len=None, sigma=0.4, guide_heads=2,
+                    causal=False, scale=0.125, parts=0):
+    """attn_bwd of out + kappa * sum(rows): kappa is the device scalar coef (guided_attn_loss
+    writes it), rows the guided forward's g buffer.  delta is left holding delta + kappa g."""
+    L = lib()
+    a = _attn_common(q, k, v, q_ld, k_ld, v_ld, batch, heads, tq, tk, key_len, causal, scale)
+    hd = heads * 64
+    cd = q.dtype
+    for name, t, ld, n in (("q", q, q_ld, tq), ("k", k, k_ld, tk), ("v", v, v_ld, tk), ("o", o, o_ld, tq),
+                           ("dout", dout, do_ld, tq), ("dq", dq, dq_ld, tq), ("dk", dk, dk_ld, tk),
+                           ("dv", dv, dv_ld, tk)):
+        _need(f"attn_bwd_guided: {name}", t, _span(ld, batch * n, hd), cd)
+    _need("attn_bwd_guided: lse", lse, batch * heads * tq, torch.float32)
+    _need("attn_bwd_guided: delta", delta, batch * heads * tq, torch.float32)
+    if key_len is not None:
+        _need("attn_bwd_guided: key_len", key_len, batch, torch.int32)
+    if coef is None:
+        raise _lib.TT2Error("attn_bwd_guided: coef required")
+    g = _attn_guide("attn_bwd_guided", rows, q_len, coef, sigma, guide_heads, batch, heads, tq)
+    a.parts = parts
+    a.o, a.dout, a.o_ld, a.do_ld = o.data_ptr(), dout.data_ptr(), o_ld, do_ld
+    a.dq, a.dk, a.dv = dq.data_ptr(), dk.data_ptr(), dv.data_ptr()
+    a.dq_ld, a.dk_ld, a.dv_ld = dq_ld, dk_ld, dv_ld
+    a.lse, a.delta = lse.data_ptr(), delta.data_ptr()
+    check(L.tt2_attn_bwd_guided(C.byref(a), C.byref(g), stream_ptr()), "tt2_attn_bwd_guided")
+
+
+def guided_attn_loss(rows, term, coef, batch, heads, tq, tk, key_len=None, q_len=None, guide_heads=2, scale=10.0,
+                     grad_scale=1.0, loss_out=None):
+    """term = scale * sum(rows of the guided heads, all layers in `rows`) / N with
+    N = len(rows) * guide_heads * sum_b Tx_b Ty_b; coef = scale * grad_scale / N (kappa of
+    attn_bwd_guided); loss_out[0] += term.  N = 0: term = coef = 0, loss_out untouched."""
+    if len(rows) > _lib.GUIDE_MAX_LAYERS:
+        raise _lib.TT2Error(f"guided_attn_loss: at most {_lib.GUIDE_MAX_LAYERS} layers")
+    a = _lib.GuideLossArgs()
+    for i, r in enumerate(rows):
+        _need(f"guided_attn_loss: rows[{i}]", r, batch * heads * tq, torch.float32)
+        a.rows[i] = r.data_ptr()
+    _need("guided_attn_loss: term", term, 1, torch.float32)
+    _need("guided_attn_loss: coef", coef, 1, torch.float32)
+    for name, t in (("key_len", key_len), ("q_len", q_len)):
+        if t is not None:
+            _need(f"guided_attn_loss: {name}", t, batch, torch.int32)
+    if loss_out is not None:
+        _need("guided_attn_loss: loss_out", loss_out, 1, torch.float32)
+    a.key_len, a.q_len, a.loss_out, a.term, a.coef = ptr(key_len), ptr(q_len), ptr(loss_out), term.data_ptr(), \
+        coef.data_ptr()
+    a.n_layers, a.batch, a.heads, a.guide_heads, a.tq, a.tk = len(rows), batch, heads, guide_heads, tq, tk
+    a.scale, a.grad_scale = scale, grad_scale
+    check(lib().tt2_guided_attn_loss(C.byref(a), stream_ptr()), "tt2_guided_attn_loss")
+
+
 def _drop_into(s, drop: Drop):
     s.drop_seed, s.drop_site, s.drop_thr, s.drop_scale = drop.fields()
 
