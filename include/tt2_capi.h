@@ -254,6 +254,54 @@ typedef struct tt2_guide_loss_args {
 } tt2_guide_loss_args;
 int tt2_guided_attn_loss(const tt2_guide_loss_args* a, hipStream_t stream);
 
+/* Alignment statistics of forwards already run (encoder-decoder attention; no attention matrix is
+ * stored): one launch for n_layers layers, each with its own q, k and saved log2-LSE (the k of
+ * layer l is usually a column slice of one wide buffer, row stride k_ld).  For layer slot i,
+ * (b, h) and query row n:
+ *   pmax[i][b*heads + h][n] = max_t P[n, t] = exp2(s_max * scale * log2(e) - lse[n])   (f32)
+ *   amax[i][b*heads + h][n] = the key index of that maximum, the LOWEST index on exact ties (int32)
+ * Keys t >= key_len[b] are masked as in tt2_attn_fwd.  Rows n >= q_len[b] and rows whose LSE is
+ * +inf (no visible key) give pmax = 0 exactly and amax = -1.  key_len and q_len may be NULL (tk /
+ * tq).  Non-causal only: causal != 0 is refused (TT2_E_INVALID), as are scale <= 0 and
+ * n_layers > TT2_GUIDE_MAX_LAYERS.  variant as in tt2_attn_args: 0 auto (bf16: the MFMA kernel,
+ * whose scores are formed exactly as the v3 forward forms them; f32: the plain kernel), 1 the
+ * plain kernel (one work group per row), 2 / 3 the MFMA kernel with 2 / 4 waves per work group. */
+typedef struct tt2_align_args {
+  const void* q[TT2_GUIDE_MAX_LAYERS];      /* per layer: [batch*tq, >= heads*64], row stride q_ld */
+  const void* k[TT2_GUIDE_MAX_LAYERS];      /* per layer: [batch*tk, >= heads*64], row stride k_ld */
+  const float* lse[TT2_GUIDE_MAX_LAYERS];   /* per layer: [batch*heads, tq] f32, as the forward saved it */
+  int64_t q_ld, k_ld;
+  const int32_t* key_len; const int32_t* q_len;   /* [batch], device (NULL: tk / tq) */
+  float* pmax;      /* [n_layers, batch*heads, tq] f32 */
+  int32_t* amax;    /* [n_layers, batch*heads, tq] int32 */
+  int32_t n_layers, batch, heads, head_dim, tq, tk, dtype, causal;
+  float scale;
+  int32_t variant;
+} tt2_align_args;
+int tt2_attn_align(const tt2_align_args* a, hipStream_t stream);
+
+/* Focus rates and phoneme durations from tt2_attn_align's output (the FastSpeech teacher
+ * procedure), one work group per utterance, fixed summation order and integer counts only, so
+ * the results are bit-identical run to run.  With Ty_b = min(tq, q_len[b]) valid rows:
+ *   focus[i][b][h] = mean over n < Ty_b of pmax[i][b*heads + h][n]     (0 if Ty_b = 0)
+ *   mode 0: sel[b] = {layer slot, head} of utterance b's greatest focus (lowest flat index
+ *           slot*heads + head on ties);  mode 1: sel[b] = {sel_layer, sel_head} for every b
+ *   sel_focus[b]    = focus of the chosen head
+ *   durations[b][t] = #{n < Ty_b : amax of the chosen head at n == t}, t < tk   (int32)
+ * durations[b][t] is exactly 0 for t >= key_len[b], and sum_t durations[b][t] = Ty_b whenever
+ * utterance b has a visible key (else 0).  n_layers * heads <= 1024. */
+typedef struct tt2_align_dur_args {
+  const float* pmax; const int32_t* amax;         /* [n_layers, batch*heads, tq] */
+  const int32_t* key_len; const int32_t* q_len;   /* [batch], device (NULL: tk / tq) */
+  float* focus;          /* [n_layers, batch, heads] f32 */
+  int32_t* sel;          /* [batch, 2] int32 */
+  float* sel_focus;      /* [batch] f32 */
+  int32_t* durations;    /* [batch, tk] int32 */
+  int32_t n_layers, batch, heads, tq, tk;
+  int32_t mode, sel_layer, sel_head;
+} tt2_align_dur_args;
+int tt2_align_durations(const tt2_align_dur_args* a, hipStream_t stream);
+
 /* ------------------------------------------------------------------ decode
  * One query row per batch element (the AR decode step):
  * out[b*o_ld + 64h ..] = softmax(scale q k^T) v over keys j < n_b of batch b,

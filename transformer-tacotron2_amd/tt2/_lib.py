@@ -183,6 +183,32 @@ SIGNATURES.update({
 })
 
 
+class AlignArgs(C.Structure):
+    """tt2_align_args: max attention weight and its key index per query row, all layers in one launch."""
+    _fields_ = [
+        ("q", vp * GUIDE_MAX_LAYERS), ("k", vp * GUIDE_MAX_LAYERS), ("lse", vp * GUIDE_MAX_LAYERS),
+        ("q_ld", i64), ("k_ld", i64), ("key_len", vp), ("q_len", vp), ("pmax", vp), ("amax", vp),
+        ("n_layers", i32), ("batch", i32), ("heads", i32), ("head_dim", i32), ("tq", i32), ("tk", i32),
+        ("dtype", i32), ("causal", i32), ("scale", f32), ("variant", i32),
+    ]
+
+
+class AlignDurArgs(C.Structure):
+    """tt2_align_dur_args: focus rates, head choice and durations from tt2_attn_align's output."""
+    _fields_ = [
+        ("pmax", vp), ("amax", vp), ("key_len", vp), ("q_len", vp),
+        ("focus", vp), ("sel", vp), ("sel_focus", vp), ("durations", vp),
+        ("n_layers", i32), ("batch", i32), ("heads", i32), ("tq", i32), ("tk", i32),
+        ("mode", i32), ("sel_layer", i32), ("sel_head", i32),
+    ]
+
+
+SIGNATURES.update({
+    "tt2_attn_align": ([C.POINTER(AlignArgs), vp], C.c_int),
+    "tt2_align_durations": ([C.POINTER(AlignDurArgs), vp], C.c_int),
+})
+
+
 class ReduceArgs(C.Structure):
     _fields_ = [("src", vp), ("dst", vp), ("ld", i64), ("rows", i32), ("cols", i32), ("beta", f32)]
 

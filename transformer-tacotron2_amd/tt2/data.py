@@ -11,11 +11,15 @@
 * ``bucket_batches``: length-bucketed, shuffled batches (similar lengths together, so
   padding -- and the masked compute it costs -- stays small);
 * ``collate``: padded id / length tensors and log-mel targets [B, T, 80] computed on the
-  GPU by ``tt2.audio.MelExtractor`` (one batched STFT per batch).
+  GPU by ``tt2.audio.MelExtractor`` (one batched STFT per batch);
+* ``extract_durations``: per-utterance phoneme durations from a trained model's alignment
+  (``TransformerTTS.durations``), written as ``<id>.npy`` plus a ``durations.json`` manifest:
+  the training targets of a non-autoregressive student.
 """
 from __future__ import annotations
 
 import csv
+import json
 import os
 import random
 import re
@@ -126,3 +130,69 @@ def collate(ds: LJSpeech, indices, extractor, device="cuda"):
     lens = torch.tensor([len(w) for w in wavs], dtype=torch.int32)
     mel, frames = extractor(audio.to(device), lens.to(device))
     return text.to(device), text_len.to(device), mel, frames.to(torch.long)
+
+
+def extract_durations(model, batches, out_dir: str, head="best"):
+    """Phoneme durations of every utterance in `batches`, an iterable (re-iterable for
+    head="dataset") of (ids, text, text_len, mel, mel_len), through
+    model.durations(text, text_len, mel, mel_len, head=...).  head:
+      "best"     each utterance's own best (layer, head);
+      "dataset"  two passes: the first accumulates the frame-weighted focus rate of every
+                 (layer, head) over all utterances (model.alignment_stats() after each
+                 durations() forward), the second uses the single head with the highest one;
+      (l, h)     that head.
+    Writes out_dir/<id>.npy (int32 [text_len]) per utterance and out_dir/durations.json:
+    {"head": ..., "utterances": {id: {"layer", "head", "focus", "frames", "phonemes"}}}.
+    Returns the manifest.  The model needs only durations() (and alignment_stats() for
+    "dataset"), so a stub drives it in tests.
+
+    Batch shapes: the engine keeps one arena of activations per distinct (B, Tx, Ty) it has run,
+    for good (about 110 KB per decoder row in bf16: about 1.1 GB at B = 16 and 650 frames), and
+    ragged batches as bucket_batches + collate make them nearly all differ: a corpus would hold
+    hundreds of arenas.  So every call here is durations(..., transient=True): an arena that the
+    call itself created is dropped again afterwards (it stays alive as the model's last forward
+    until the next one, so at most two are held), while the arena of a shape the model already
+    ran (its training shape, a captured step's) is left alone.  The batches are not padded or
+    otherwise changed: padding an utterance further changes what the encoder's convolutions see
+    at its end, and with it the alignment."""
+    os.makedirs(out_dir, exist_ok=True)
+    use = head
+    dataset_focus = None
+    if isinstance(head, str) and head == "dataset":
+        if iter(batches) is batches:
+            raise ValueError('extract_durations: head="dataset" reads the batches twice; pass a list, not an iterator')
+        num = None
+        frames = 0.0
+        layers = None
+        for _, text, text_len, mel, mel_len in batches:
+            model.durations(text, text_len, mel, mel_len, head="best", transient=True)
+            st = model.alignment_stats()
+            w = torch.as_tensor(mel_len).to(st.focus.device, torch.float64).clamp(max=mel.shape[1])
+            part = (st.focus.to(torch.float64) * w[None, :, None]).sum(1)   # [L, H], frame-weighted
+            num = part if num is None else num + part
+            frames += float(w.sum())
+            layers = tuple(st.layers)
+        if num is None:
+            raise ValueError("extract_durations: no batches")
+        flat = int(torch.argmax(num.reshape(-1)))   # the lowest flat index on ties
+        use = (int(layers[flat // num.shape[1]]), flat % num.shape[1])
+        dataset_focus = float(num.reshape(-1)[flat]) / max(frames, 1.0)
+    elif not (isinstance(head, str) and head == "best"):
+        use = (int(head[0]), int(head[1]))
+    manifest = {"head": head if isinstance(head, str) else list(use), "utterances": {}}
+    if dataset_focus is not None:
+        manifest["dataset_head"] = list(use)
+        manifest["dataset_focus"] = dataset_focus
+    for ids, text, text_len, mel, mel_len in batches:
+        r = model.durations(text, text_len, mel, mel_len, head=use, transient=True)
+        dur, hd, fc = r.durations.cpu().numpy(), r.head.cpu().numpy(), r.focus.cpu().numpy()
+        tl = [int(x) for x in torch.as_tensor(text_len).cpu()]
+        ml = [int(x) for x in torch.as_tensor(mel_len).cpu()]
+        for b, uid in enumerate(ids):
+            d = np.ascontiguousarray(dur[b, :tl[b]], dtype=np.int32)
+            np.save(os.path.join(out_dir, f"{uid}.npy"), d)
+            manifest["utterances"][str(uid)] = {"layer": int(hd[b, 0]), "head": int(hd[b, 1]), "focus": float(fc[b]),
+                                                "frames": min(ml[b], mel.shape[1]), "phonemes": tl[b]}
+    with open(os.path.join(out_dir, "durations.json"), "w") as f:
+        json.dump(manifest, f, indent=1, sort_keys=True)
+    return manifest

@@ -399,6 +399,43 @@ class TTSEngine:
                              self.cfg.n_heads, A.Ty, A.Tx, key_len=A["text_len"], q_len=A["mel_len"],
                              guide_heads=g["heads"], scale=g["scale"], grad_scale=grad_scale, loss_out=loss_out)
 
+    # ------------------------------------------------------------ alignment statistics
+    def align_layers(self, layers=None) -> tuple:
+        c = self.cfg
+        ls = tuple(range(c.n_dec)) if layers is None else tuple(sorted({int(l) % c.n_dec for l in layers}))
+        if not ls:
+            raise ValueError("alignment statistics: at least one decoder layer")
+        if len(ls) > GUIDE_MAX_LAYERS:
+            raise ValueError(f"alignment statistics: at most {GUIDE_MAX_LAYERS} layers")
+        return ls
+
+    def align_stats(self, A: "Arena", layers: tuple, head=None) -> dict:
+        """Two launches on the current stream, no host synchronisation: tt2_attn_align over the
+        saved cross-attention inputs of decoder layers `layers` (A["dcq{l}"], the layer's key
+        columns of A["mkv"], A["dclse{l}"]), then tt2_align_durations.  head: None (the best head
+        per utterance) or a (slot in `layers`, head) pair.  backward() only reads those three
+        buffers (they are the q, k and lse inputs of the cross-attention backward; its outputs go
+        to g_cq and g_mkv), so this works after a forward, a full step or a captured step's
+        replay.  The result tensors are plain allocations, not arena buffers: no arena changes
+        and no captured step is invalidated."""
+        c = self.cfg
+        d, H, n = c.d_model, c.n_heads, len(layers)
+        B, Tx, Ty = A.B, A.Tx, A.Ty
+        dev, f32, i32 = self.dev, torch.float32, torch.int32
+        out = dict(pmax=torch.empty(n, B, H, Ty, dtype=f32, device=dev),
+                   amax=torch.empty(n, B, H, Ty, dtype=i32, device=dev),
+                   focus=torch.empty(n, B, H, dtype=f32, device=dev),
+                   sel=torch.empty(B, 2, dtype=i32, device=dev),
+                   sel_focus=torch.empty(B, dtype=f32, device=dev),
+                   durations=torch.empty(B, Tx, dtype=i32, device=dev))
+        mkv = A["mkv"]
+        ops.attn_align([A[f"dcq{l}"] for l in layers], [mkv[:, 2 * d * l:] for l in layers],
+                       [A[f"dclse{l}"] for l in layers], out["pmax"], out["amax"], d, c.n_dec * 2 * d, B, H, Ty, Tx,
+                       key_len=A["text_len"], q_len=A["mel_len"], scale=1.0 / math.sqrt(c.head_dim))
+        ops.align_durations(out["pmax"], out["amax"], out["focus"], out["sel"], out["sel_focus"], out["durations"],
+                            n, B, H, Ty, Tx, key_len=A["text_len"], q_len=A["mel_len"], head=head)
+        return out
+
     # ------------------------------------------------------------ GEMM helpers
     def _lin(self, x, w, out, m, n, k, bias=None, act=ACT_NONE, drop=NO_DROP, res=None, ldx=None, ldo=None,
              a_conv=None, beta=0.0, **fuse):

@@ -29,6 +29,7 @@ from __future__ import annotations
 
 import math
 import os
+from typing import NamedTuple
 
 import torch
 import torch.nn as nn
@@ -39,6 +40,21 @@ from .capture import StepCapture
 from .config import TTSConfig
 from .engine import Arena, TTSEngine
 from .params import from_state_dict, grads_to_state_dict_names, to_state_dict
+
+
+class AlignmentStats(NamedTuple):
+    """alignment_stats(): per decoder layer in `layers`, batch element, head and frame."""
+    pmax: torch.Tensor     # [L, B, H, Ty] f32: max_t P[n, t] (0 for frames past mel_len)
+    argmax: torch.Tensor   # [L, B, H, Ty] int32: its phoneme index, lowest on ties (-1 for those frames)
+    focus: torch.Tensor    # [L, B, H] f32: mean of pmax over the valid frames (the focus rate)
+    layers: tuple          # the decoder layers, in the order of the first axis
+
+
+class Durations(NamedTuple):
+    """durations(): phoneme durations read off the chosen encoder-decoder attention head."""
+    durations: torch.Tensor   # [B, Tx] int32: frames per phoneme (0 past text_len); rows sum to mel_len
+    head: torch.Tensor        # [B, 2] int32: the (decoder layer, head) used for each utterance
+    focus: torch.Tensor       # [B] f32: that head's focus rate
 
 
 class _TTSForward(torch.autograd.Function):
@@ -109,6 +125,7 @@ class TransformerTTS(nn.Module):
         self._last: Arena | None = None
         self._graphs: dict = {}
         self._loss_bufs: dict = {}
+        self._align_lut: dict = {}   # durations(): layer-slot -> decoder-layer tables on the device
         self._slot_names = list(e.lay.slots)
         self.metrics = None   # StepMetrics (enable_metrics / TT2_METRICS): one JSONL line per step
         if os.environ.get("TT2_METRICS"):
@@ -422,6 +439,65 @@ class TransformerTTS(nn.Module):
         valid = torch.arange(Ty, device=a.device)[None, :] < mel_len.to(a.device)[:, None]
         mx = a.amax(-1)
         return (mx * valid).sum(1) / valid.sum(1).clamp_min(1)
+
+    def alignment_stats(self, layers=None) -> AlignmentStats:
+        """The alignment of the last forward in numbers, without storing any attention matrix:
+        for each decoder layer in `layers` (default all), head and frame, the greatest
+        encoder-decoder attention weight and the phoneme that holds it, and the focus rate
+        F = mean over the valid frames of that weight for each (layer, head) -- near 1 once a
+        head has learned to align.  One kernel launch for all the layers plus one reduction
+        launch, on the current stream, with no host synchronisation.  It works on the saved
+        query, memory keys and log-sum-exp of the last forward, which the backward only reads,
+        so it may be called after forward(), after train_step() and after a captured step's
+        replay; its results are fresh tensors outside the arena."""
+        if self._last is None:
+            raise RuntimeError("alignment_stats() needs a forward first")
+        ls = self.engine.align_layers(layers)
+        r = self.engine.align_stats(self._last, ls)
+        return AlignmentStats(r["pmax"], r["amax"], r["focus"], ls)
+
+    def durations(self, text, text_len, mel, mel_len, head="best", layers=None, transient=False) -> Durations:
+        """Phoneme durations for a non-autoregressive student (the FastSpeech teacher
+        procedure): a teacher-forced forward with dropout off and no autograd graph, then
+        d[b, t] = the number of frames n < mel_len[b] whose greatest attention weight sits on
+        phoneme t, taken from one encoder-decoder attention head.  head="best": per utterance,
+        the (layer, head) among `layers` (default all) with the highest focus rate; head=(l, h):
+        that head for every utterance.  Parameters, BatchNorm statistics, the dropout seed and
+        the optimizer state are untouched and the module's train / eval mode is restored.
+        transient=True: if this call is the first to run the shape (B, Tx, Ty), the arena of
+        activations it created is dropped from the engine afterwards instead of being kept for
+        good (it lives on as the last forward until the next one).  A corpus of ragged batches,
+        each of its own shape, would otherwise keep one arena per batch
+        (tt2.data.extract_durations passes it).  Arenas that existed before the call stay."""
+        e = self.engine
+        ls = e.align_layers(layers)
+        fixed = None
+        if not (isinstance(head, str) and head == "best"):
+            l, h = int(head[0]) % self.cfg.n_dec, int(head[1])
+            if l not in ls or not 0 <= h < self.cfg.n_heads:
+                raise ValueError(f"durations: head {tuple(head)} is outside layers {ls} / {self.cfg.n_heads} heads")
+            fixed = (ls.index(l), h)
+        shape = (text.shape[0], text.shape[1], mel.shape[1])
+        fresh = transient and shape not in e.arenas
+        was_training, pipelined = self.training, e.pipeline_opt
+        try:
+            self.train(False)
+            e.pipeline_opt = False   # a pipelined step's pending Adam stays pending
+            with torch.no_grad():
+                A = self._run_forward(text, text_len, mel, mel_len)
+        finally:
+            e.pipeline_opt = pipelined
+            self.train(was_training)
+        r = e.align_stats(A, ls, head=fixed)
+        if fresh:
+            e.arenas.pop(shape, None)   # (self._last keeps A until the next forward)
+        sel = r["sel"]
+        if ls != tuple(range(len(ls))):   # layer slots -> decoder layers, on the device
+            lut = self._align_lut.get(ls)
+            if lut is None:
+                lut = self._align_lut[ls] = torch.tensor(ls, dtype=torch.int32, device=e.dev)
+            sel = torch.stack((lut[sel[:, 0].long()], sel[:, 1]), dim=1)
+        return Durations(r["durations"], sel, r["sel_focus"])
 
     # ------------------------------------------------------------ training
     def configure_optimizer(self, **kw):

@@ -438,6 +438,72 @@ def guided_attn_loss(rows, term, coef, batch, heads, tq, tk, key_len=None, q_len
     check(lib().tt2_guided_attn_loss(C.byref(a), stream_ptr()), "tt2_guided_attn_loss")
 
 
+def attn_align(qs, ks, lses, pmax, amax, q_ld, k_ld, batch, heads, tq, tk, key_len=None, q_len=None,
+               causal=False, scale=0.125, variant=None):
+    """pmax[i, b*heads+h, n] = max_t P[n, t] and amax[...] = its key index (lowest on ties; -1 and 0
+    for rows past q_len or without a visible key) of len(qs) forwards already run, in one launch:
+    qs[i], ks[i] (row strides q_ld, k_ld; ks[i] may be a column slice of one wide buffer) and the
+    saved lses[i] of layer slot i (tt2_align_args).  Non-causal only."""
+    n = len(qs)
+    if n > _lib.GUIDE_MAX_LAYERS:
+        raise _lib.TT2Error(f"attn_align: at most {_lib.GUIDE_MAX_LAYERS} layers")
+    if len(ks) != n or len(lses) != n:
+        raise _lib.TT2Error("attn_align: one q, k and lse per layer")
+    a = _lib.AlignArgs()
+    hd = heads * 64
+    cd = qs[0].dtype if n else torch.bfloat16
+    if cd not in (torch.bfloat16, torch.float32):
+        raise _lib.TT2Error(f"attn_align: q / k must be bf16 or f32, got {cd}")
+    for i in range(n):
+        _need(f"attn_align: q[{i}]", qs[i], _span(q_ld, batch * tq, hd), cd)
+        _need(f"attn_align: k[{i}]", ks[i], _span(k_ld, batch * tk, hd), cd)
+        _need(f"attn_align: lse[{i}]", lses[i], batch * heads * tq, torch.float32)
+        a.q[i], a.k[i], a.lse[i] = qs[i].data_ptr(), ks[i].data_ptr(), lses[i].data_ptr()
+    _need("attn_align: pmax", pmax, n * batch * heads * tq, torch.float32)
+    _need("attn_align: amax", amax, n * batch * heads * tq, torch.int32)
+    for name, t in (("key_len", key_len), ("q_len", q_len)):
+        if t is not None:
+            _need(f"attn_align: {name}", t, batch, torch.int32)
+    a.q_ld, a.k_ld, a.key_len, a.q_len = q_ld, k_ld, ptr(key_len), ptr(q_len)
+    a.pmax, a.amax = pmax.data_ptr(), amax.data_ptr()
+    a.n_layers, a.batch, a.heads, a.head_dim, a.tq, a.tk = n, batch, heads, 64, tq, tk
+    a.dtype = _lib.DT_BF16 if cd == torch.bfloat16 else _lib.DT_F32
+    a.causal, a.scale = int(causal), scale   # (causal: refused by the library, as the guided calls are)
+    a.variant = ATTN_VARIANT if variant is None else variant
+    check(lib().tt2_attn_align(C.byref(a), stream_ptr()), "tt2_attn_align")
+    return pmax, amax
+
+
+def align_durations(pmax, amax, focus, sel, sel_focus, durations, n_layers, batch, heads, tq, tk, key_len=None,
+                    q_len=None, head=None):
+    """From attn_align's output: focus[i, b, h] = mean of pmax over the valid rows, the chosen head
+    per utterance into sel [batch, 2] = (layer slot, head) (head=None: the greatest focus; head=(slot,
+    h): that one for every utterance), its focus into sel_focus [batch], and durations[b, t] = the
+    number of valid rows of the chosen head whose amax is t (tt2_align_dur_args).  Deterministic."""
+    if n_layers > _lib.GUIDE_MAX_LAYERS:
+        raise _lib.TT2Error(f"align_durations: at most {_lib.GUIDE_MAX_LAYERS} layers")
+    a = _lib.AlignDurArgs()
+    _need("align_durations: pmax", pmax, n_layers * batch * heads * tq, torch.float32)
+    _need("align_durations: amax", amax, n_layers * batch * heads * tq, torch.int32)
+    _need("align_durations: focus", focus, n_layers * batch * heads, torch.float32)
+    _need("align_durations: sel", sel, 2 * batch, torch.int32)
+    _need("align_durations: sel_focus", sel_focus, batch, torch.float32)
+    _need("align_durations: durations", durations, batch * tk, torch.int32)
+    for name, t in (("key_len", key_len), ("q_len", q_len)):
+        if t is not None:
+            _need(f"align_durations: {name}", t, batch, torch.int32)
+    a.pmax, a.amax, a.key_len, a.q_len = pmax.data_ptr(), amax.data_ptr(), ptr(key_len), ptr(q_len)
+    a.focus, a.sel, a.sel_focus, a.durations = focus.data_ptr(), sel.data_ptr(), sel_focus.data_ptr(), \
+        durations.data_ptr()
+    a.n_layers, a.batch, a.heads, a.tq, a.tk = n_layers, batch, heads, tq, tk
+    if head is None:
+        a.mode = 0
+    else:
+        a.mode, a.sel_layer, a.sel_head = 1, int(head[0]), int(head[1])
+    check(lib().tt2_align_durations(C.byref(a), stream_ptr()), "tt2_align_durations")
+    return durations
+
+
 def _drop_into(s, drop: Drop):
     s.drop_seed, s.drop_site, s.drop_thr, s.drop_scale = drop.fields()
 
