@@ -617,6 +617,10 @@ int tt2_cast2d(const void* src, int src_dtype, int64_t src_ld, void* dst, int ds
  * mel_after [batch*t, n_mels] f32, target f32 [batch, t, n_mels].
  * loss_out[4] = (total, mse_before, mse_after, bce_stop); gradients: g_heads
  * (f32, heads_ld; mel cols carry before + after terms), g_after (grad_dtype).
+ * Frame (b, j) is valid iff j < mel_len[b]; the terms are means over the N = sum_b
+ * min(max(mel_len[b], 0), t) valid frames, the stop label is 1 at j == mel_len[b] - 1 (none within
+ * a sequence cut off at t), padded frames get zero gradients, N == 0 gives zero losses and
+ * gradients, and g_heads' columns above n_mels are written as zeros.
  * Replaces SURVEY 8(a) a10. */
 typedef struct tt2_loss_args {
   const float* heads; const float* mel_after; const float* target;
@@ -669,7 +673,8 @@ typedef struct tt2_adam_args {
 } tt2_adam_args;
 size_t tt2_adam_workspace_size(void);
 int tt2_adam_step(const tt2_adam_args* a, hipStream_t stream);
-/* parts[0 .. nparts) = partial sums of g[i]^2 over g[0, n) (fixed split: reproducible) */
+/* parts[0 .. nparts) = partial sums of g[i]^2 over g[0, n) (fixed split: reproducible); n == 0
+ * writes zeros and g may then be NULL */
 int tt2_sumsq_parts(const float* g, int64_t n, float* parts, int32_t nparts, hipStream_t stream);
 /* step += 1; seed += 1 (either may be NULL: the pipelined optimizer bumps the dropout seed at the
  * end of a step and the step counter once the deferred Adam has run) */
