@@ -47,6 +47,34 @@ def test_gemm_col_stats(m, cin, cout, T, rows):
         assert torch.allclose(st[r, 1], m2, rtol=1e-4, atol=1e-4 * blk.shape[0]), (r, (st[r, 1] - m2).abs().max())
 
 
+@pytest.mark.parametrize("m", [256, 257])
+def test_gemm_col_stats_on_a_v10_plan(m):
+    """A col_stats request whose plan is v10 (forced: variant 16, n % 256 == 0): v10 carries no
+    statistics, so the launch takes v7's LDS-image epilogue and its 256-row chunks."""
+    n, k, rows = 256, 64, 256
+    g = torch.Generator().manual_seed(m)
+    x = torch.randn(m, k, generator=g).bfloat16().cuda()
+    w = (torch.randn(n, k, generator=g) / k ** 0.5).bfloat16().cuda()
+    b = (0.1 * torch.randn(n, generator=g)).cuda()
+    y = torch.empty(m, n, dtype=torch.bfloat16, device="cuda")
+    assert ops.gemm_stats_rows(x, w, y, m, n, k, k, k, n, bias=b, variant=16) == rows
+    R = (m + rows - 1) // rows
+    st = torch.full((2 * R * n,), float("nan"), device="cuda")
+    ops.gemm(x, w, y, m, n, k, k, k, n, bias=b, variant=16, col_stats=st)
+    y_ref = torch.empty_like(y)   # v7's LDS-image epilogue without the statistics
+    ops.gemm(x, w, y_ref, m, n, k, k, k, n, bias=b, variant=14)
+    torch.cuda.synchronize()
+    assert torch.equal(y, y_ref)
+    yd = y.double().cpu()
+    st = st.view(R, 2, n).double().cpu()
+    for r in range(R):
+        blk = yd[r * rows:(r + 1) * rows]
+        mu = blk.mean(0)
+        m2 = ((blk - mu) ** 2).sum(0)
+        assert torch.allclose(st[r, 0], mu, rtol=1e-5, atol=1e-6), (r, (st[r, 0] - mu).abs().max())
+        assert torch.allclose(st[r, 1], m2, rtol=1e-4, atol=1e-4 * blk.shape[0]), (r, (st[r, 1] - m2).abs().max())
+
+
 @pytest.mark.parametrize("m,T", [(12800, 800), (1000, 125), (2048, 128)])
 def test_batchnorm_fwd_from_gemm_stats(m, T):
     cin = cout = 512

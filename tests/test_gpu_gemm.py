@@ -69,6 +69,21 @@ def test_gemm_epilogue(dtype, variant, n, splits):
     assert rel(out, ref) < tol
 
 
+@pytest.mark.parametrize("m", [64, 257])
+def test_gemm_v8_request_with_unaligned_c_rows(m):
+    """A request the plan gives to v8 (variant 15) whose C starts one element past a 16-B
+    boundary: v8 stores whole 16-B chunks, so the launch takes v7 with per-element stores."""
+    n, k = 72, 64
+    g = torch.Generator().manual_seed(m)
+    A, B = _mk((m, k), torch.bfloat16, g), _mk((n, k), torch.bfloat16, g)
+    buf = torch.full((m * n + 8,), float("nan"), dtype=torch.bfloat16, device="cuda")
+    out = buf[1:1 + m * n].view(m, n)
+    assert out.data_ptr() % 16 == 2
+    ops.gemm(A, B, out, m, n, k, k, k, n, variant=15)
+    assert rel(out, A.double() @ B.double().t()) < 8e-3
+    assert torch.isnan(buf[0]).item() and torch.isnan(buf[1 + m * n:]).all().item()   # nothing outside C
+
+
 @pytest.mark.parametrize("variant", [0, 13, 14])
 @pytest.mark.parametrize("k", [64, 128, 192, 520])
 @pytest.mark.parametrize("tile_op", ["res", "gate", "none"])

@@ -70,6 +70,22 @@ def test_gemm11_dgrad_matches_v7(mnk, epi):
     assert ((c11.double() - ref).norm() / ref.norm()).item() < 1e-2
 
 
+@pytest.mark.parametrize("m", [256, 257])
+def test_gemm11_request_with_f32_residual_runs_on_v7(m):
+    """Variant 17 forced on the activation-gradient layout with an f32 residual: v11 stages bf16
+    residual tiles only, so the launch takes v7."""
+    n, k = 128, 64
+    g = torch.Generator(device="cuda").manual_seed(m)
+    A = torch.randn(m, k, device="cuda", generator=g).bfloat16()
+    B = (torch.randn(k, n, device="cuda", generator=g) / k ** 0.5).bfloat16()
+    X = torch.randn(m, n, device="cuda", generator=g)
+    c17 = _run(A, B, m, n, k, True, dict(res=X, ldr=n), 17)
+    torch.cuda.synchronize()
+    assert not torch.isnan(c17).any()
+    ref = A.double() @ B.double() + X.double()
+    assert ((c17.double() - ref).norm() / ref.norm()).item() < 1e-2
+
+
 def test_gemm11_is_the_auto_choice():
     """The forward NT product with K <= 1024 runs v11 under auto: same bits as variant 17."""
     m, n, k = 12800, 512, 512

@@ -2,7 +2,7 @@
 
 Needs the in-step phase build of libtt2 (tools/build_variant.sh phase -DTT2_PHASE=1, then
 TT2_LIB=abl/phase.so): every v7 / grouped-v7 / v10 work group then writes, into its launch-probe
-record, s_memtime stamps of its first MFMA wave (gemm.hip, TT2_SPAN_W = 32 slots): entry, the start
+record, s_memtime stamps of its first MFMA wave (gemm_common.h, TT2_SPAN_W = 32 slots): entry, the start
 of K steps 0..11 and the end of their MFMA issue, the end of the K loop, the C image written, the
 work group's barrier, the C stores issued, and (last wave) the stores drained.  The step is captured
 with the probe armed for every GEMM (as tools/step_census.py), replayed, and each launch's records

@@ -1,4 +1,4 @@
-// In-kernel timeline of the v7 GEMM (dev tool): builds gemm.hip with its stamp hooks defined, runs a
+// In-kernel timeline of the v7 GEMM (dev tool): builds the GEMM units with their stamp hooks defined, runs a
 // shape, and prints the average per-K-step split (s_memtime cycles, wave 0 of every
 // workgroup): wait = vmcnt + barrier, issue = LDS-DMA issue, comp = fragment reads +
 // MFMA issue, plus the epilogue and the spread of workgroup start times.
@@ -10,16 +10,23 @@
 #include <cstdlib>
 #include <vector>
 
-// the stamp hooks gemm.hip leaves empty in the library build (wave 0 of every workgroup)
+// the stamp hooks gemm_v7.h leaves empty in the library build (wave 0 of every workgroup)
 __device__ unsigned long long g_st[4096 * 64 * 4];
 #define G7_STAMP(t, slot)                                                                            \
   if (threadIdx.x == 0 && (t) < 64)                                                                  \
     g_st[((size_t)(blockIdx.x + gridDim.x * blockIdx.y) * 64 + (t)) * 4 + (slot)] = __builtin_amdgcn_s_memtime();
 #define G7_RT(slot)                                                                                  \
   if (threadIdx.x == 0) g_st[(size_t)blockIdx.x * 64 * 4 + 63 * 4 + (slot)] = __builtin_amdgcn_s_memrealtime();
+// the GEMM units tt2_gemm dispatches to, as one unity source
+#include "../transformer-tacotron2_amd/csrc/gemm_probe.hip"
+#include "../transformer-tacotron2_amd/csrc/gemm_v1.hip"
+#include "../transformer-tacotron2_amd/csrc/gemm_skinny.hip"
+#include "../transformer-tacotron2_amd/csrc/gemm_v2v7v11.hip"
+#include "../transformer-tacotron2_amd/csrc/gemm_v8.hip"
+#include "../transformer-tacotron2_amd/csrc/gemm_v10.hip"
 #include "../transformer-tacotron2_amd/csrc/gemm.hip"
 #include "../transformer-tacotron2_amd/csrc/runtime.cpp"
-// gemm.hip's grouped launch sizes a LayerNorm finalize with this (norm.hip); unused here
+// gemm_v7_impl.h's grouped launch sizes a LayerNorm finalize with this (norm.hip); unused here
 extern "C" size_t tt2_layernorm_bwd_workspace_size(const tt2_ln_args*) { return 0; }
 
 int main(int argc, char** argv) {

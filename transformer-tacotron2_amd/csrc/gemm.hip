@@ -1,4 +1,6 @@
-// gemm.hip -- MFMA GEMM with fused epilogues and implicit-im2col operands.
+// gemm.hip -- the GEMM's host side: request validation, the planner, the route from a request to
+// the one kernel that runs it, and tt2_gemm.  The kernels live one family per unit
+// (gemm_common.h has the map); this unit holds no device code.
 //
 //   C[m, n] = epi( alpha * sum_k A(m, k) * B(n, k) )
 //
@@ -12,1266 +14,11 @@
 // output frame (b,t) is the overlapping window x[(b*T+t-pad)*C ...], i.e. an
 // operand with ld = C and a per-chunk validity test 0 <= t + tap - pad < T.
 //
-// Tiling: 128x128 output tile, BK = 32, 256 threads = 4 waves (2 x 2), each wave
-// 64x64 = 4x4 MFMA 16x16 blocks.  Global -> registers -> LDS double buffer with
-// the next tile's loads in flight during the current tile's MFMAs (one barrier
-// per K step).  K-contiguous tiles are read with 16-B ds_read, M/N-contiguous
-// tiles with ds_read_b64_tr_b16 (gfx950 transposing LDS read).
-// Split-K (gridDim.z > 1) writes raw f32 partial slabs to the workspace and a
-// second kernel (gemm_splitk_reduce) sums them in a fixed order (bitwise
-// reproducible) and applies the epilogue.
-#include <hip/hip_ext.h>
+#include "gemm_common.h"
 
-#include <algorithm>
-#include <cstdlib>
-#include <string>
-#include <vector>
+using tt2g::Epilogue;
+using tt2g::Operand;
 
-#include "tt2_common.h"
-#include "tt2_capi.h"
-#include "tt2_internal.h"
-
-namespace {
-
-// Launch probe (measurement): when armed, the next main GEMM kernel launched on this
-// thread records a start / stop event pair at its own dispatch and completion
-// (hipExtLaunchKernelGGL), i.e. the kernel's execution time as rocprofv3 reports it,
-// without the gaps an event recorded around the launch on the stream adds.
-struct ProbeSlot { hipEvent_t start, stop; bool used; };
-thread_local std::vector<ProbeSlot> g_probe;
-thread_local int g_probe_armed = -1;
-// Beside the events, every probe-capable kernel records its own span on the device's
-// constant-rate wall clock: each workgroup writes {its start, the end of its last wave after
-// that wave's stores completed} to its own pair of a slot's record (plain stores, no shared
-// address), and tt2_probe_span_ms takes the earliest start and the latest end.  Nothing is
-// added to the stream, so the span of a launch inside a replayed step graph is its in-step
-// duration, with no event node (and its dispatch gap) around it.  Records come from one
-// pool per thread, allocated (zeroed) by the first tt2_probe_arm, outside any capture.
-// Record width per work group: {start, end}; the in-step phase build (TT2_PHASE) adds
-// s_memtime stamps (slot 2: entry; 3 + 2t / 4 + 2t: K step t's start / after its MFMAs,
-// t < 12; 27..30: the epilogue's points, G7_STAMP; 31: the last wave's stores drained).
-#ifdef TT2_PHASE
-#define TT2_SPAN_W 32
-constexpr int64_t PROBE_SPAN_PAIRS = 1 << 17;
-#else
-#define TT2_SPAN_W 2
-constexpr int64_t PROBE_SPAN_PAIRS = 1 << 20;
-#endif
-thread_local unsigned long long* g_span = nullptr;
-thread_local int64_t g_span_used = 0;
-thread_local std::vector<std::pair<int64_t, int>> g_span_rec;   // per slot: pool offset, work groups
-// per slot: work groups per launch when one probed call goes out as consecutive launches (a
-// capped grouped grid): the span is then the sum of the launches' own spans, as rocprofv3
-// times each dispatch (0: one launch)
-thread_local std::vector<int> g_span_chunk;
-
-int probe_take(hipEvent_t& e0, hipEvent_t& e1, unsigned long long*& span, int groups) {
-  span = nullptr;
-  if (g_probe_armed < 0) return -1;
-  const int slot = g_probe_armed;
-  ProbeSlot& p = g_probe[slot];
-  e0 = p.start;
-  e1 = p.stop;
-  p.used = true;
-  if (g_span && groups > 0 && g_span_used + groups <= PROBE_SPAN_PAIRS) {
-    span = g_span + TT2_SPAN_W * g_span_used;
-    g_span_rec[slot] = {g_span_used, groups};
-    g_span_used += groups;
-  }
-  g_probe_armed = -1;
-  return slot;
-}
-
-TT2_DEV void span_begin(unsigned long long* span, int* done) {
-  if (span && threadIdx.x == 0) {
-    *done = 0;
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // visible before the first barrier
-    span[TT2_SPAN_W * blockIdx.x] = wall_clock64();
-#ifdef TT2_PHASE
-    span[TT2_SPAN_W * blockIdx.x + 2] = __builtin_amdgcn_s_memtime();
-#endif
-  }
-}
-// every wave once its own stores have completed (stores count in vmcnt on gfx9); the last
-// wave of the workgroup to get here writes the end
-TT2_DEV void span_end(unsigned long long* span, int* done, int waves) {
-  if (span) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    if ((threadIdx.x & 63) == 0 && atomicAdd(done, 1) == waves - 1) {
-#ifdef TT2_PHASE
-      span[TT2_SPAN_W * blockIdx.x + 31] = __builtin_amdgcn_s_memtime();
-#endif
-      span[TT2_SPAN_W * blockIdx.x + 1] = wall_clock64();
-    }
-  }
-}
-
-// The probe around one main-kernel launch.  Eager: the events ride in the kernel's own
-// dispatch (hipExtLaunchKernelGGL, ext()) and the kernel records its span.  Under stream
-// capture (a hipGraph of the step, bench.py's graph leg) only the span: nothing is added to
-// the graph, and every replay re-records the launch's in-step duration.
-struct ProbeScope {
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  unsigned long long* span = nullptr;   // the kernel's own span record (see g_span)
-  int slot = -1;
-  ProbeScope(hipStream_t s, int groups) {
-    if ((slot = probe_take(e0, e1, span, groups)) < 0) return;
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(s, &cs) == hipSuccess && cs == hipStreamCaptureStatusActive) e0 = e1 = nullptr;
-    (void)hipGetLastError();
-  }
-  bool ext() const { return e0 != nullptr; }
-  void chunk(int wgs) const { if (slot >= 0) g_span_chunk[slot] = wgs; }
-};
-
-
-constexpr int BM = 128, BN = 128, BK = 32, NT = 256;
-
-struct EpiParams {
-  void* c; int64_t ldc; int c_dt;
-  const float* bias;
-  const void* res; int64_t ldr; int res_dt;
-  const void* gate; int64_t ldg; int gate_dt; float gate_scale;
-  float alpha, beta;
-  int act;
-  DropDesc drop;
-  int n_log;  // logical N for dropout index (m * n_log + n)
-  int vec;    // every row of C/res/gate/bias is 16-B aligned at 8-column boundaries
-  float* ksum; float ksum_beta;   // fused row sums of op(A) over k (v2, M-contiguous A)
-  int main_only;                  // split-K: skip the reduce launch (measurement hook)
-  float* cstats;                  // v7 LDS-image path: 256-row chunk column moments (tt2_gemm_args col_stats)
-  // v7 LDS-image path: C is a BatchNorm backward's dout; its chunk sums of dpre, dpre * xhat go
-  // to bnb.part (tt2_gemm_args bn_bwd)
-  struct {
-    const bf16* y; const float* mean; const float* rstd; const float* gamma; const float* beta;
-    float* part;
-    DropDesc drop;
-    int act;
-  } bnb;
-};
-
-// fixed-order split-K slab reduce + epilogue (defined after epi_store8) and its grid size
-__global__ void gemm_splitk_reduce(const float* ws, int splits, EpiParams E, int M, int N);
-int splitk_blocks(int M, int N, const EpiParams& E);
-
-TT2_DEV float ld_any(const void* p, int64_t i, int dt) {
-  if (dt == TT2_F16) return (float)reinterpret_cast<const f16*>(p)[i];
-  return dt == TT2_BF16 ? (float)reinterpret_cast<const bf16*>(p)[i] : reinterpret_cast<const float*>(p)[i];
-}
-TT2_DEV void st_any(void* p, int64_t i, int dt, float v) {
-  if (dt == TT2_F16) reinterpret_cast<f16*>(p)[i] = (f16)v;
-  else if (dt == TT2_BF16) reinterpret_cast<bf16*>(p)[i] = (bf16)v;
-  else reinterpret_cast<float*>(p)[i] = v;
-}
-
-TT2_DEV float epi_value(const EpiParams& e, uint32_t seed, int m, int n, float v) {
-  v *= e.alpha;
-  if (e.bias) v += e.bias[n];
-  if (e.res) v += ld_any(e.res, (int64_t)m * e.ldr + n, e.res_dt);
-  if (e.act == ACT_RELU) v = fmaxf(v, 0.f);
-  else if (e.act == ACT_TANH) v = tanhf(v);
-  if (e.gate) v = ld_any(e.gate, (int64_t)m * e.ldg + n, e.gate_dt) != 0.f ? v * e.gate_scale : 0.f;
-  if (e.drop.thr) v = drop_apply(e.drop, seed, (uint32_t)((int64_t)m * e.n_log + n), v);
-  if (e.beta != 0.f) v += e.beta * ld_any(e.c, (int64_t)m * e.ldc + n, e.c_dt);
-  return v;
-}
-
-struct OpDesc {
-  const void* p;
-  int64_t ld;
-  int outer_max, inner_max;   // bounds of the outer (strided) and inner (contiguous) index
-  int conv_t, conv_c, conv_pad;
-};
-
-// Load one 16-B chunk at (outer, inner) with bounds/conv masking.
-template <typename T>
-TT2_DEV ChunkV<T> load_op_chunk(const OpDesc& d, int outer, int inner) {
-  constexpr int E = Chunk<T>::N;
-  const T* base = reinterpret_cast<const T*>(d.p);
-  if (outer >= d.outer_max || inner >= d.inner_max) return zero_chunk<T>();
-  if (d.conv_t > 0) {
-    const int t = outer % d.conv_t;
-    const int ts = t + inner / d.conv_c - d.conv_pad;
-    if (ts < 0 || ts >= d.conv_t) return zero_chunk<T>();
-    // chunks never straddle taps (conv_c % E == 0, checked on the host)
-    return ld_chunk<T>(base + (int64_t)outer * d.ld + inner - (int64_t)d.conv_pad * d.conv_c);
-  }
-  const T* p = base + (int64_t)outer * d.ld + inner;
-  if (inner + E <= d.inner_max) return ld_chunk<T>(p);
-  ChunkV<T> c = zero_chunk<T>();
-  for (int e = 0; e < E; ++e)
-    if (inner + e < d.inner_max) c.e[e] = p[e];
-  return c;
-}
-
-// LDS tile geometry for one operand.
-//  KC (K-contiguous): tile[128][BK + pad], row = m (or n)
-//  MC (M-contiguous): tile[BK][128 + pad], row = k
-template <typename T, bool KC> struct TileGeo;
-template <typename T> struct TileGeo<T, true> {
-  static constexpr int LD = BK + Chunk<T>::N;   // +16 B per row
-  static constexpr int ELEMS = 128 * LD;
-  static constexpr int CPR = BK / Chunk<T>::N;   // chunks per row
-};
-template <typename T> struct TileGeo<T, false> {
-  static constexpr int LD = 128 + Chunk<T>::N;
-  static constexpr int ELEMS = BK * LD;
-  static constexpr int CPR = 128 / Chunk<T>::N;
-};
-
-template <typename T> struct NCh { static constexpr int V = 128 * BK / Chunk<T>::N / NT; };
-
-// global tile -> registers.  tile_r0: first m/n of the tile; k0: first k.
-template <typename T, bool KC>
-TT2_DEV void g2r(ChunkV<T> (&r)[NCh<T>::V], const OpDesc& d, int tile_r0, int k0, int tid) {
-  using G = TileGeo<T, KC>;
-#pragma unroll
-  for (int i = 0; i < NCh<T>::V; ++i) {
-    const int c = tid + NT * i;
-    const int row = c / G::CPR, cc = c % G::CPR;
-    if (KC) r[i] = load_op_chunk<T>(d, tile_r0 + row, k0 + cc * Chunk<T>::N);
-    else r[i] = load_op_chunk<T>(d, k0 + row, tile_r0 + cc * Chunk<T>::N);
-  }
-}
-template <typename T, bool KC>
-TT2_DEV void r2s(const ChunkV<T> (&r)[NCh<T>::V], T* tile, int tid) {
-  using G = TileGeo<T, KC>;
-#pragma unroll
-  for (int i = 0; i < NCh<T>::V; ++i) {
-    const int c = tid + NT * i;
-    const int row = c / G::CPR, cc = c % G::CPR;
-    st_chunk<T>(tile + row * G::LD + cc * Chunk<T>::N, r[i]);
-  }
-}
-
-// fragment for rows [r0, r0+16) of the tile (r = m or n), k in [0, 32)
-template <typename T, bool KC>
-TT2_DEV void s2f(Frag8<T>& f, const T* tile, int r0, int lane) {
-  using G = TileGeo<T, KC>;
-  if (KC) frag_row(f, tile + (r0 + (lane & 15)) * G::LD + 8 * (lane >> 4));
-  else frag_col(f, tile, G::LD, 8 * (lane >> 4), r0, lane);
-}
-
-template <typename T, bool AK, bool BKC>
-__global__ __launch_bounds__(NT) void gemm_kernel(OpDesc A, OpDesc B, EpiParams E, int M, int N, int K,
-                                                  int k_split, float* ws) {
-  using GA = TileGeo<T, AK>;
-  using GB = TileGeo<T, BKC>;
-  __shared__ __attribute__((aligned(16))) T smem[2 * (GA::ELEMS + GB::ELEMS)];
-  constexpr int STAGE = GA::ELEMS + GB::ELEMS;
-
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int wm = wave >> 1, wn = wave & 1;
-  const int m0 = blockIdx.y * BM, n0 = blockIdx.x * BN;
-  const int kb = blockIdx.z * k_split;
-  const int ke = min(K, kb + k_split);
-  // bound the k dimension of both operands to this split
-  if (AK) A.inner_max = ke; else A.outer_max = ke;
-  if (BKC) B.inner_max = ke; else B.outer_max = ke;
-  const int nkt = (ke - kb + BK - 1) / BK;
-
-  f32x4 acc[4][4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-  ChunkV<T> ra[NCh<T>::V], rb[NCh<T>::V];
-  g2r<T, AK>(ra, A, m0, kb, tid);
-  g2r<T, BKC>(rb, B, n0, kb, tid);
-  r2s<T, AK>(ra, smem, tid);
-  r2s<T, BKC>(rb, smem + GA::ELEMS, tid);
-  __syncthreads();
-
-  for (int kt = 0; kt < nkt; ++kt) {
-    const int cur = kt & 1;
-    const bool more = kt + 1 < nkt;
-    if (more) {
-      g2r<T, AK>(ra, A, m0, kb + (kt + 1) * BK, tid);
-      g2r<T, BKC>(rb, B, n0, kb + (kt + 1) * BK, tid);
-    }
-    Frag8<T> fa[4], fb[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) s2f<T, AK>(fa[i], smem + cur * STAGE, wm * 64 + 16 * i, lane);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) s2f<T, BKC>(fb[j], smem + cur * STAGE + GA::ELEMS, wn * 64 + 16 * j, lane);
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) mma16(fa[i], fb[j], acc[i][j]);
-    if (more) {
-      r2s<T, AK>(ra, smem + (cur ^ 1) * STAGE, tid);
-      r2s<T, BKC>(rb, smem + (cur ^ 1) * STAGE + GA::ELEMS, tid);
-    }
-    __syncthreads();
-  }
-
-  // epilogue: acc[i][j][r] = C[m0 + wm*64 + 16i + 4*(lane>>4) + r][n0 + wn*64 + 16j + (lane&15)]
-  const uint32_t seed = E.drop.thr ? *E.drop.seed : 0u;
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int m = m0 + wm * 64 + 16 * i + 4 * (lane >> 4) + r;
-        const int n = n0 + wn * 64 + 16 * j + (lane & 15);
-        if (m < M && n < N) {
-          if (ws) ws[((int64_t)blockIdx.z * M + m) * N + n] = acc[i][j][r];
-          else st_any(E.c, (int64_t)m * E.ldc + n, E.c_dt, epi_value(E, seed, m, n, acc[i][j][r]));
-        }
-      }
-}
-
-
-template <typename T, bool AK, bool BKC>
-hipError_t launch_t(const OpDesc& A, const OpDesc& B, const EpiParams& E, int M, int N, int K, int splits,
-                    float* ws, hipStream_t s) {
-  int k_split = K;
-  if (splits > 1) {
-    k_split = ((K + splits - 1) / splits + BK - 1) / BK * BK;
-    splits = (K + k_split - 1) / k_split;
-  }
-  dim3 grid((N + BN - 1) / BN, (M + BM - 1) / BM, splits);
-  hipLaunchKernelGGL((gemm_kernel<T, AK, BKC>), grid, dim3(NT), 0, s, A, B, E, M, N, K, k_split,
-                     splits > 1 ? ws : nullptr);
-  if (splits > 1 && !E.main_only)
-    hipLaunchKernelGGL(gemm_splitk_reduce, dim3(splitk_blocks(M, N, E)), dim3(256), 0, s, ws, splits, E, M, N);
-  return hipGetLastError();
-}
-
-// =====================================================================================
-// v2 (bf16): BK = 64, LDS-DMA staging (global_load_lds_dwordx4: each lane's 16-B chunk
-// lands at lds_base + 16*lane), two LDS stages, one barrier per K-tile, XOR swizzles
-// applied on the per-lane GLOBAL source address so the lane-linear LDS image reads
-// conflict-free with ds_read_b128 (K-contiguous tiles) and ds_read_b64_tr_b16
-// (M/N-contiguous tiles).  Out-of-range / conv-padding chunks load from a zero page.
-// Epilogue: accumulators -> LDS (f32) -> 16-B vectorised epilogue + stores.
-// =====================================================================================
-constexpr int BK2 = 64;
-constexpr int TILE_BYTES = 128 * BK2 * 2;               // 16 KB per operand tile
-constexpr int STAGE_BYTES = 2 * TILE_BYTES;             // A + B
-constexpr int EPI_LD = 132;                             // f32 words per staged C row (pad: conflict-free)
-constexpr int SMEM2 = (2 * STAGE_BYTES > 128 * EPI_LD * 4) ? 2 * STAGE_BYTES : 128 * EPI_LD * 4;
-
-__device__ __attribute__((aligned(64))) uint4 g_zero_page[64];
-
-typedef __attribute__((address_space(1))) void gvoid_t;
-typedef __attribute__((address_space(3))) void lvoid_t;
-
-// swizzle of the 16-B chunk index for an M/N-contiguous tile row k (256-B rows)
-TT2_DEV int mc_swz(int k) { return ((k & 3) << 1) ^ (((k >> 3) & 1) << 3); }
-
-// Per-lane LDS-DMA source: the chunk's address, or the zero page when the chunk is out
-// of range (or reads conv padding).  Branch-free per lane (a select), so the DMA issue
-// is not wrapped in exec-mask branches; the conv test is behind a uniform branch.
-TT2_DEV const void* chunk_src(const OpDesc& d, int outer, int inner) {
-  bool ok = (outer < d.outer_max) & (inner < d.inner_max);
-  int64_t off = (int64_t)outer * d.ld + inner;
-  if (d.conv_t > 0) {
-    const int ts = outer % d.conv_t + inner / d.conv_c - d.conv_pad;
-    ok = ok & (ts >= 0) & (ts < d.conv_t);
-    off -= (int64_t)d.conv_pad * d.conv_c;
-  }
-  const void* p = reinterpret_cast<const bf16*>(d.p) + off;
-  return ok ? p : (const void*)g_zero_page;
-}
-
-// issue this wave's 4 of the 16 LDS-DMA instructions of one 128 x 64 operand tile
-template <bool KC>
-TT2_DEV void issue_tile(const OpDesc& d, char* lds_tile, int r0, int k0, int lane, int wave) {
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int inst = wave * 4 + i;
-    const void* src;
-    if (KC) {
-      const int row = inst * 8 + (lane >> 3);
-      const int gc = (lane & 7) ^ (row & 7);
-      src = chunk_src(d, r0 + row, k0 + gc * 8);
-    } else {
-      const int kr = inst * 4 + (lane >> 4);
-      const int gc = (lane & 15) ^ mc_swz(kr);
-      src = chunk_src(d, k0 + kr, r0 + gc * 8);
-    }
-    __builtin_amdgcn_global_load_lds((gvoid_t*)src, (lvoid_t*)(lds_tile + inst * 1024), 16, 0, 0);
-  }
-}
-
-// fragment (8 consecutive k of row r0 + (lane&15)) for k-step kk (0/1) of the 64-deep tile
-template <bool KC>
-TT2_DEV void frag2(Frag8<bf16>& f, const char* tile, int r0, int kk, int lane) {
-  if (KC) {
-    const int row = r0 + (lane & 15);
-    const int h = 4 * kk + (lane >> 4);
-    f.v = *reinterpret_cast<const bf16x8*>(tile + row * 128 + ((h ^ (row & 7)) << 4));
-  } else {
-    const int g = lane >> 4, q = (lane >> 2) & 3, p = lane & 3;
-    const int c = (r0 + 4 * p) >> 3;
-    typedef __attribute__((address_space(3))) short4v lds_s4;
-    const int k_lo = 32 * kk + 8 * g + q;
-    const int k_hi = k_lo + 4;
-    const char* a0 = tile + k_lo * 256 + ((c ^ mc_swz(k_lo)) << 4) + ((p & 1) << 3);
-    const char* a1 = tile + k_hi * 256 + ((c ^ mc_swz(k_hi)) << 4) + ((p & 1) << 3);
-    short4v lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4*)(a0));
-    short4v hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4*)(a1));
-    union { short s[8]; bf16x8 v; } u;
-    u.s[0] = lo[0]; u.s[1] = lo[1]; u.s[2] = lo[2]; u.s[3] = lo[3];
-    u.s[4] = hi[0]; u.s[5] = hi[1]; u.s[6] = hi[2]; u.s[7] = hi[3];
-    f.v = u.v;
-  }
-}
-
-// 8 consecutive elements of a row from a bf16 or f32 tensor (16-B aligned)
-TT2_DEV void ld8_any(const void* p, int64_t off, int dt, float (&o)[8]) {
-  if (dt == TT2_BF16) {
-    const bf16x8 x = *reinterpret_cast<const bf16x8*>(reinterpret_cast<const bf16*>(p) + off);
-#pragma unroll
-    for (int j = 0; j < 8; ++j) o[j] = (float)x[j];
-  } else {
-    const float* q = reinterpret_cast<const float*>(p) + off;
-    const f32x4 a = *reinterpret_cast<const f32x4*>(q), b = *reinterpret_cast<const f32x4*>(q + 4);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) { o[j] = a[j]; o[4 + j] = b[j]; }
-  }
-}
-
-// Chunk epilogue: 8 consecutive outputs of row m starting at column n0.  Full,
-// aligned chunks (E.vec) take 16-B loads/stores with every option tested once
-// per chunk; edge chunks fall back to the per-element path.
-// pre_b: alpha and bias were already applied to v (v7's prefetched bias; E.vec, full chunk)
-// Vectorised chunk epilogue without the store: o = epi(v) for a full, aligned chunk (E.vec).
-// res_l / gate_l: the chunk of a bf16 residual / gate already staged in LDS by v7's loader
-// waves.
-TT2_DEV void unpack_lds8(const void* p, float (&t)[8]) {
-  const bf16x8 x = *reinterpret_cast<const bf16x8*>(p);
-#pragma unroll
-  for (int j = 0; j < 8; ++j) t[j] = (float)x[j];
-}
-TT2_DEV void epi_calc8(const EpiParams& E, uint32_t seed, int m, int n0, const float (&v)[8], bool pre_b,
-                       float (&o)[8], const void* res_l = nullptr, const void* gate_l = nullptr) {
-  const int64_t off = (int64_t)m * E.ldc + n0;
-  float t[8];
-#pragma unroll
-  for (int j = 0; j < 8; ++j) o[j] = pre_b ? v[j] : v[j] * E.alpha;
-  if (E.bias && !pre_b) {
-    const f32x4 a = *reinterpret_cast<const f32x4*>(E.bias + n0), b = *reinterpret_cast<const f32x4*>(E.bias + n0 + 4);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) { o[j] += a[j]; o[4 + j] += b[j]; }
-  }
-  if (E.res) {
-    if (res_l) unpack_lds8(res_l, t);
-    else ld8_any(E.res, (int64_t)m * E.ldr + n0, E.res_dt, t);
-#pragma unroll
-    for (int j = 0; j < 8; ++j) o[j] += t[j];
-  }
-  if (E.act == ACT_RELU) {
-#pragma unroll
-    for (int j = 0; j < 8; ++j) o[j] = fmaxf(o[j], 0.f);
-  } else if (E.act == ACT_TANH) {
-#pragma unroll
-    for (int j = 0; j < 8; ++j) o[j] = tanhf(o[j]);
-  }
-  if (E.gate) {
-    if (gate_l) unpack_lds8(gate_l, t);
-    else ld8_any(E.gate, (int64_t)m * E.ldg + n0, E.gate_dt, t);
-#pragma unroll
-    for (int j = 0; j < 8; ++j) o[j] = t[j] != 0.f ? o[j] * E.gate_scale : 0.f;
-  }
-  if (E.drop.thr) {
-    drop_apply8(E.drop, seed, (uint32_t)((int64_t)m * E.n_log + n0), o);
-  }
-  if (E.beta != 0.f) {
-    ld8_any(E.c, off, E.c_dt, t);
-#pragma unroll
-    for (int j = 0; j < 8; ++j) o[j] += E.beta * t[j];
-  }
-}
-
-TT2_DEV void epi_store8(const EpiParams& E, uint32_t seed, int m, int n0, int N, const float (&v)[8],
-                        bool pre_b = false) {
-  const int64_t off = (int64_t)m * E.ldc + n0;
-  if (E.vec && n0 + 8 <= N) {
-    float o[8];
-    epi_calc8(E, seed, m, n0, v, pre_b, o);
-    if (E.c_dt == TT2_BF16) {
-      bf16x8 x;
-#pragma unroll
-      for (int j = 0; j < 8; ++j) x[j] = (bf16)o[j];
-      *reinterpret_cast<bf16x8*>(reinterpret_cast<bf16*>(E.c) + off) = x;
-    } else {
-      float* c = reinterpret_cast<float*>(E.c) + off;
-      *reinterpret_cast<f32x4*>(c) = f32x4{o[0], o[1], o[2], o[3]};
-      *reinterpret_cast<f32x4*>(c + 4) = f32x4{o[4], o[5], o[6], o[7]};
-    }
-    return;
-  }
-  for (int j = 0; j < 8; ++j)
-    if (n0 + j < N) st_any(E.c, off + j, E.c_dt, epi_value(E, seed, m, n0 + j, v[j]));
-}
-
-TT2_DEV void splitk_reduce_body(const float* ws, int splits, const EpiParams& E, int M, int N, int bx, int nbx) {
-  const int64_t total = (int64_t)M * N;
-  const uint32_t seed = E.drop.thr ? *E.drop.seed : 0u;
-  if (E.ksum) {   // [splits][M] k-sum partials after the C slabs, fixed split order
-    const float* kp = ws + splits * total;
-    for (int64_t m = bx * (int64_t)blockDim.x + threadIdx.x; m < M; m += (int64_t)nbx * blockDim.x) {
-      float v = 0.f;
-      for (int z = 0; z < splits; ++z) v += kp[z * (int64_t)M + m];
-      E.ksum[m] = E.ksum_beta != 0.f ? E.ksum_beta * E.ksum[m] + v : v;
-    }
-  }
-  if ((N & 7) == 0 && E.vec) {
-    // 8 consecutive columns per thread: 2 x 16-B slab loads per split (fixed split order),
-    // then the vectorised chunk epilogue (16-B bias / residual / gate / C loads and stores)
-    const int64_t t8 = total / 8;
-    for (int64_t i = bx * (int64_t)blockDim.x + threadIdx.x; i < t8; i += (int64_t)nbx * blockDim.x) {
-      const f32x4* w0 = reinterpret_cast<const f32x4*>(ws) + 2 * i;
-      f32x4 lo = w0[0], hi = w0[1];
-      for (int z = 1; z < splits; ++z) {
-        const f32x4* wz = reinterpret_cast<const f32x4*>(ws + z * total) + 2 * i;
-        lo += wz[0];
-        hi += wz[1];
-      }
-      const float v[8] = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-      int m, n;
-      if (total < (1ll << 31)) {   // 32-bit division (the usual case) instead of a 64-bit one per chunk
-        const uint32_t e = 8u * (uint32_t)i;
-        m = (int)(e / (uint32_t)N);
-        n = (int)(e - (uint32_t)m * (uint32_t)N);
-      } else {
-        m = (int)(8 * i / N);
-        n = (int)(8 * i % N);
-      }
-      epi_store8(E, seed, m, n, N, v);
-    }
-    return;
-  }
-  if ((N & 3) == 0) {
-    // 4 consecutive columns per thread (16-B partial-slab loads), fixed split order
-    const int64_t t4 = total / 4;
-    for (int64_t i = bx * (int64_t)blockDim.x + threadIdx.x; i < t4; i += (int64_t)nbx * blockDim.x) {
-      // two accumulators, 4 slab loads in flight per step (fixed order per element)
-      f32x4 v = reinterpret_cast<const f32x4*>(ws)[i], w = f32x4{0.f, 0.f, 0.f, 0.f};
-      int z = 1;
-      for (; z + 3 < splits; z += 4) {
-        const f32x4 a0 = reinterpret_cast<const f32x4*>(ws + z * total)[i];
-        const f32x4 a1 = reinterpret_cast<const f32x4*>(ws + (z + 1) * total)[i];
-        const f32x4 a2 = reinterpret_cast<const f32x4*>(ws + (z + 2) * total)[i];
-        const f32x4 a3 = reinterpret_cast<const f32x4*>(ws + (z + 3) * total)[i];
-        v += a0 + a2;
-        w += a1 + a3;
-      }
-      for (; z < splits; ++z) v += reinterpret_cast<const f32x4*>(ws + z * total)[i];
-      v += w;
-      const int m = (int)(4 * i / N), n = (int)(4 * i % N);
-#pragma unroll
-      for (int j = 0; j < 4; ++j) st_any(E.c, (int64_t)m * E.ldc + n + j, E.c_dt, epi_value(E, seed, m, n + j, v[j]));
-    }
-    return;
-  }
-  for (int64_t i = bx * (int64_t)blockDim.x + threadIdx.x; i < total; i += (int64_t)nbx * blockDim.x) {
-    float v = 0.f;
-    for (int z = 0; z < splits; ++z) v += ws[z * total + i];
-    const int m = (int)(i / N), n = (int)(i % N);
-    st_any(E.c, (int64_t)m * E.ldc + n, E.c_dt, epi_value(E, seed, m, n, v));
-  }
-}
-
-__global__ void gemm_splitk_reduce(const float* ws, int splits, EpiParams E, int M, int N) {
-  splitk_reduce_body(ws, splits, E, M, N, blockIdx.x, gridDim.x);
-}
-
-// reduce grid: one 256-thread block per 256 work items of splitk_reduce_body's path (8, 4 or 1
-// output elements per thread); a grid of one block per 256 ELEMENTS left 7 of 8 blocks of the
-// 8-wide path with nothing to do (dispatching them cost more than the reduce)
-int splitk_blocks(int M, int N, const EpiParams& E) {
-  const int64_t per = ((N & 7) == 0 && E.vec) ? 8 : ((N & 3) == 0 ? 4 : 1);
-  const int64_t items = std::max<int64_t>(((int64_t)M * N + per - 1) / per, M);
-  const int64_t nb = (items + 255) / 256;
-  return (int)(nb < 4096 ? nb : 4096);
-}
-
-template <bool AK, bool BKC>
-__global__ __launch_bounds__(NT, 2) void gemm2_kernel(OpDesc A, OpDesc B, EpiParams E, int M, int N, int K,
-                                                      int k_split, float* ws, int ntm, int ntn) {
-  __shared__ __attribute__((aligned(1024))) char smem[SMEM2];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int wm = wave >> 1, wn = wave & 1;
-  // XCD-aware tile order: blocks b and b+8 share an XCD, so give each XCD a
-  // contiguous run of tiles (walking n for a fixed m: the A row panel stays in that L2).
-  const int nt = ntm * ntn;
-  const int bid = blockIdx.x;
-  const int q = nt / 8, rr = nt % 8, x = bid % 8;
-  const int tile = (x < rr ? x * (q + 1) : rr * (q + 1) + (x - rr) * q) + bid / 8;
-  const int m0 = (tile / ntn) * BM, n0 = (tile % ntn) * BN;
-  const int kb = blockIdx.y * k_split;
-  const int ke = min(K, kb + k_split);
-  if (AK) A.inner_max = ke; else A.outer_max = ke;
-  if (BKC) B.inner_max = ke; else B.outer_max = ke;
-  const int nkt = (ke - kb + BK2 - 1) / BK2;
-  const bool do_ks = !AK && E.ksum && (tile % ntn) == 0;   // one n-tile per m-tile sums A over k
-  float ks[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-
-  f32x4 acc[4][4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-  issue_tile<AK>(A, smem, m0, kb, lane, wave);
-  issue_tile<BKC>(B, smem + TILE_BYTES, n0, kb, lane, wave);
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-
-  for (int kt = 0; kt < nkt; ++kt) {
-    const char* sa = smem + (kt & 1) * STAGE_BYTES;
-    const char* sb = sa + TILE_BYTES;
-    if (kt + 1 < nkt) {
-      char* na = smem + ((kt + 1) & 1) * STAGE_BYTES;
-      issue_tile<AK>(A, na, m0, kb + (kt + 1) * BK2, lane, wave);
-      issue_tile<BKC>(B, na + TILE_BYTES, n0, kb + (kt + 1) * BK2, lane, wave);
-    }
-#pragma unroll
-    for (int kk = 0; kk < 2; ++kk) {
-      Frag8<bf16> fa[4], fb[4];
-#pragma unroll
-      for (int i = 0; i < 4; ++i) frag2<AK>(fa[i], sa, wm * 64 + 16 * i, kk, lane);
-#pragma unroll
-      for (int j = 0; j < 4; ++j) frag2<BKC>(fb[j], sb, wn * 64 + 16 * j, kk, lane);
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) mma16(fa[i], fb[j], acc[i][j]);
-    }
-    if (!AK && do_ks) {
-      // rows 4*(tid>>4) .. +3 of the [64 k][128 m] A image, m-chunk tid & 15
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int kr = 4 * (tid >> 4) + r;
-        const bf16x8 v = *reinterpret_cast<const bf16x8*>(sa + kr * 256 + (((tid & 15) ^ mc_swz(kr)) << 4));
-#pragma unroll
-        for (int j = 0; j < 8; ++j) ks[j] += (float)v[j];
-      }
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-  }
-  if (!AK && do_ks) {
-    // reduce over the 16 k-groups: lanes l, l^16, l^32, l^48, then the 4 waves via LDS
-    float* red = reinterpret_cast<float*>(smem);
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      ks[j] += __shfl_xor(ks[j], 16, 64);
-      ks[j] += __shfl_xor(ks[j], 32, 64);
-    }
-    if (lane < 16) {
-#pragma unroll
-      for (int j = 0; j < 8; ++j) red[(wave * 16 + lane) * 8 + j] = ks[j];
-    }
-    __syncthreads();
-    if (tid < 128) {
-      const int cc = tid >> 3, j = tid & 7, m = m0 + tid;
-      const float v = (red[(0 * 16 + cc) * 8 + j] + red[(1 * 16 + cc) * 8 + j]) +
-                      (red[(2 * 16 + cc) * 8 + j] + red[(3 * 16 + cc) * 8 + j]);
-      if (m < M) {
-        if (ws) ws[(int64_t)gridDim.y * M * N + (int64_t)blockIdx.y * M + m] = v;
-        else E.ksum[m] = E.ksum_beta != 0.f ? E.ksum_beta * E.ksum[m] + v : v;
-      }
-    }
-    __syncthreads();
-  }
-
-  // stage C (f32) through LDS: row-major [128][EPI_LD]
-  float* cs = reinterpret_cast<float*>(smem);
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-#pragma unroll
-      for (int r = 0; r < 4; ++r)
-        cs[(wm * 64 + 16 * i + 4 * (lane >> 4) + r) * EPI_LD + wn * 64 + 16 * j + (lane & 15)] = acc[i][j][r];
-  __syncthreads();
-  const uint32_t seed = (!ws && E.drop.thr) ? *E.drop.seed : 0u;
-#pragma unroll 2
-  for (int it = 0; it < 8; ++it) {
-    const int id = tid + NT * it;
-    const int row = id >> 4, c8 = (id & 15) * 8;
-    const int m = m0 + row, n = n0 + c8;
-    if (m >= M || n >= N) continue;
-    float v[8];
-    const f32x4 lo = *reinterpret_cast<const f32x4*>(cs + row * EPI_LD + c8);
-    const f32x4 hi = *reinterpret_cast<const f32x4*>(cs + row * EPI_LD + c8 + 4);
-    v[0] = lo[0]; v[1] = lo[1]; v[2] = lo[2]; v[3] = lo[3];
-    v[4] = hi[0]; v[5] = hi[1]; v[6] = hi[2]; v[7] = hi[3];
-    if (ws) {
-      float* w = ws + ((int64_t)blockIdx.y * M + m) * N + n;
-      if (n + 8 <= N && (N % 4) == 0) {
-        *reinterpret_cast<f32x4*>(w) = lo;
-        *reinterpret_cast<f32x4*>(w + 4) = hi;
-      } else {
-        for (int j = 0; j < 8; ++j)
-          if (n + j < N) w[j] = v[j];
-      }
-    } else {
-      epi_store8(E, seed, m, n, N, v);
-    }
-  }
-}
-
-// =====================================================================================
-// skinny-M (decode, M <= 64) bf16: out[M, N] = X[M, K] W[N, K]^T.  The problem is a
-// latency-bound weight stream: every workgroup owns 16 output columns, its 4 waves split
-// K, and each lane issues its WHOLE slice of W (NCH 16-B chunks) before anything else,
-// then its X chunks (or the LayerNorm prologue), so the kernel pays about one memory
-// round trip instead of one per 32-deep K step.  One MFMA 16x16x32 per 16 rows x 16
-// columns x 32 k; cross-wave sums go through LDS.  Decode-step epilogues: KV-cache
-// scatter (QKV projection), scaled positional encoding (pre-net projection) and the
-// frame emit (mel/stop heads: mel_seq / stop_seq / previous frame, then the last
-// workgroup to finish advances the device step counter).
-// =====================================================================================
-constexpr int SK_COLS = 16;
-
-// Decode-step fusions carried by the skinny kernel (tt2_gemm_args a_ln_* / kv_* / pe_* / emit_*).
-struct SkinnyFuse {
-  const bf16* br; const float* gamma; const float* beta; bf16* h_out; float eps;   // LN prologue (gamma != 0)
-  void* kv; const int32_t* kv_t; int kv_col0; int64_t kv_bstride, kv_ld;           // KV scatter (kv != 0)
-  const float* pe; const float* pe_alpha; const int32_t* pe_t;                     // + alpha * pe[t][n]
-  float* emit_mel; float* emit_stop; void* emit_prev; int32_t* emit_t; uint32_t* emit_seed;
-  int32_t* emit_done; int emit_nmels, emit_tmax;                                   // frame emit (heads)
-  const float* emit_stop_bias; int32_t* emit_stop_len; float emit_stop_thr;        // stop injection / tracking
-};
-
-constexpr int SK_LN_LD = 512 + 8;   // bf16 per LDS row of the normalised A (16-B pad)
-
-// element type of the skinny path: bf16 (the engine's dtype) or f16 (the fp16 decode step)
-template <typename TE> struct SkT;
-template <> struct SkT<bf16> {
-  typedef bf16x8 V;
-  static TT2_DEV f32x4 mma(V a, V b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0); }
-};
-template <> struct SkT<f16> {
-  typedef f16x8 V;
-  static TT2_DEV f32x4 mma(V a, V b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0); }
-};
-
-template <typename TE, int NCH, bool LN, int MR>
-__global__ __launch_bounds__(NT) void gemm_skinny_kernel(const TE* X, int64_t ldx, const TE* W, int64_t ldw,
-                                                         EpiParams E, int M, int N, int K, SkinnyFuse F,
-                                                         float* slab, int kper) {
-  static_assert(!LN || (MR == 2 && __is_same(TE, bf16)), "LN prologue: bf16, m <= 32");
-  typedef typename SkT<TE>::V V8;
-  __shared__ float red[4][16 * MR][SK_COLS + 1];
-  extern __shared__ __attribute__((aligned(16))) bf16 s_h[];   // [32][SK_LN_LD] when F.gamma (K == 512)
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int n0 = blockIdx.x * SK_COLS;
-  const int r = lane & 15, g = lane >> 4;
-  const int n = n0 + r;
-  const bool nok = n < N;
-  // device scalars of the epilogue, issued up front
-  const uint32_t seed = E.drop.thr ? *E.drop.seed : 0u;
-  const int kv_t = F.kv ? *F.kv_t : 0;
-  const int pe_t = F.pe ? *F.pe_t : 0;
-  const float pe_al = F.pe ? *F.pe_alpha : 0.f;
-  const int em_t = F.emit_mel ? *F.emit_t : 0;
-  const TE* wrow = W + (int64_t)(nok ? n : 0) * ldw;
-  // MR blocks of 16 rows: block q covers rows 16 q + r
-  const TE* xr[MR];
-  bool rok[MR];
-#pragma unroll
-  for (int q = 0; q < MR; ++q) {
-    rok[q] = 16 * q + r < M;
-    xr[q] = X + (int64_t)(rok[q] ? 16 * q + r : 0) * ldx;
-  }
-  union U { uint4 u; V8 v; };
-  const uint4 z4 = make_uint4(0, 0, 0, 0);
-  f32x4 acc[MR];
-#pragma unroll
-  for (int q = 0; q < MR; ++q) acc[q] = f32x4{0.f, 0.f, 0.f, 0.f};
-  // split-K (slab != 0): workgroup row blockIdx.y takes k in [kbeg, kend) and stores its raw
-  // partial sums to slab[blockIdx.y][m][n] (f32, no epilogue; tt2_ln_combine sums them)
-  const int kbeg = slab ? blockIdx.y * kper : 0;
-  const int kend = slab ? min(K, kbeg + kper) : K;
-  float e_bias = 0.f, e_res[MR], e_pe = 0.f;
-#pragma unroll
-  for (int q = 0; q < MR; ++q) e_res[q] = 0.f;
-  const int ecol = threadIdx.x & 15, erow = threadIdx.x >> 4, enn = n0 + ecol;
-  for (int ks = kbeg; ks < kend; ks += 4 * NCH * 32) {
-    const int kb = ks + wave * (NCH * 32);
-    U w[NCH], a[MR][NCH];
-    // (1) this lane's whole W slice: branch-free (an out-of-range chunk reads the zero page)
-#pragma unroll
-    for (int c = 0; c < NCH; ++c) {
-      const int kk = kb + 32 * c + 8 * g;
-      w[c].u = *reinterpret_cast<const uint4*>(nok && kk < kend ? (const void*)(wrow + kk) : (const void*)g_zero_page);
-    }
-    if constexpr (LN) {
-      // (2a) h = LN(x + br) for the (<= 32) rows (K == 512, one pass): rows wave, wave + 4, ...,
-      // every load issued before the first reduction; h goes to LDS (the A operand) and,
-      // from workgroup 0, to F.h_out (the next residual)
-      const int c0 = lane * 8;
-      U xa[8], xb[8];
-#pragma unroll
-      for (int u = 0; u < 8; ++u) {
-        const int row = min(wave + 4 * u, M - 1);
-        xa[u].u = *reinterpret_cast<const uint4*>(X + (int64_t)row * ldx + c0);
-        xb[u].u = *reinterpret_cast<const uint4*>(F.br + (int64_t)row * ldx + c0);
-      }
-      const f32x4 g0 = *reinterpret_cast<const f32x4*>(F.gamma + c0), g1 = *reinterpret_cast<const f32x4*>(F.gamma + c0 + 4);
-      const f32x4 b0 = *reinterpret_cast<const f32x4*>(F.beta + c0), b1 = *reinterpret_cast<const f32x4*>(F.beta + c0 + 4);
-#pragma unroll
-      for (int u = 0; u < 8; ++u) {
-        const int row = wave + 4 * u;
-        float v[8], sum = 0.f;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) { v[j] = (float)xa[u].v[j] + (float)xb[u].v[j]; sum += v[j]; }
-        const float mu = wave_sum(sum) / K;
-        float sq = 0.f;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) { const float d = v[j] - mu; sq += d * d; }
-        const float rs = rsqrtf(wave_sum(sq) / K + F.eps);
-        bf16x8 h;
-#pragma unroll
-        for (int j = 0; j < 8; ++j)
-          h[j] = (bf16)((v[j] - mu) * rs * (j < 4 ? g0[j] : g1[j - 4]) + (j < 4 ? b0[j] : b1[j - 4]));
-        if (row < M) {
-          *reinterpret_cast<bf16x8*>(s_h + row * SK_LN_LD + c0) = h;
-          if (blockIdx.x == 0) *reinterpret_cast<bf16x8*>(F.h_out + (int64_t)row * K + c0) = h;
-        }
-      }
-      __syncthreads();
-#pragma unroll
-      for (int c = 0; c < NCH; ++c) {
-        const int kk = kb + 32 * c + 8 * g;
-        const bool ok = kk < K;
-#pragma unroll
-        for (int q = 0; q < MR; ++q)
-          a[q][c].u = (rok[q] && ok) ? *reinterpret_cast<const uint4*>(s_h + (16 * q + r) * SK_LN_LD + kk) : z4;
-      }
-    } else {
-      // (2b) the X chunks, also all in flight
-#pragma unroll
-      for (int c = 0; c < NCH; ++c) {
-        const int kk = kb + 32 * c + 8 * g;
-#pragma unroll
-        for (int q = 0; q < MR; ++q)
-          a[q][c].u = *reinterpret_cast<const uint4*>(rok[q] && kk < kend ? (const void*)(xr[q] + kk)
-                                                                          : (const void*)g_zero_page);
-      }
-      // keep every load above the first MFMA (the scheduler would otherwise interleave
-      // them and pay one memory round trip per pair)
-      __builtin_amdgcn_sched_barrier(0);
-    }
-    if (ks == kbeg && !slab) {
-      // the epilogue's own operands (bias, residual, PE row), in flight behind the
-      // operand loads instead of a second round trip after the reduction
-      const bool ec = enn < N;
-      if (E.bias && ec) e_bias = E.bias[enn];
-      if (E.res && ec) {
-#pragma unroll
-        for (int q = 0; q < MR; ++q)
-          if (erow + 16 * q < M) e_res[q] = ld_any(E.res, (int64_t)(erow + 16 * q) * E.ldr + enn, E.res_dt);
-      }
-      if (F.pe && ec) e_pe = pe_al * F.pe[(int64_t)pe_t * N + enn];
-    }
-#pragma unroll
-    for (int c = 0; c < NCH; ++c)
-#pragma unroll
-      for (int q = 0; q < MR; ++q) acc[q] = SkT<TE>::mma(a[q][c].v, w[c].v, acc[q]);
-  }
-  // acc layout: row 4*(lane>>4) + i, col lane & 15
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int q = 0; q < MR; ++q) red[wave][16 * q + 4 * g + i][r] = acc[q][i];
-  __syncthreads();
-  if (slab) {
-#pragma unroll
-    for (int hrow = 0; hrow < MR; ++hrow) {
-      const int m = erow + 16 * hrow;
-      if (m < M && enn < N)
-        slab[((int64_t)blockIdx.y * M + m) * N + enn] =
-            (red[0][m][ecol] + red[1][m][ecol]) + (red[2][m][ecol] + red[3][m][ecol]);
-    }
-    return;
-  }
-  // bias / residual were prefetched: the epilogue proper runs without them
-  EpiParams Ep = E;
-  Ep.bias = nullptr;
-  Ep.res = nullptr;
-  Ep.alpha = 1.f;
-#pragma unroll
-  for (int hrow = 0; hrow < MR; ++hrow) {
-    const int row = erow + 16 * hrow, col = ecol;
-    const int m = row, nn = enn;
-    if (m < M && nn < N) {
-      const float v = (red[0][row][col] + red[1][row][col]) + (red[2][row][col] + red[3][row][col]);
-      float y = epi_value(Ep, seed, m, nn, E.alpha * v + e_bias + e_res[hrow]);
-      y += e_pe;
-      st_any(E.c, (int64_t)m * E.ldc + nn, E.c_dt, y);
-      // a row past the batch stride (t >= t_max: a replay beyond the cache) is not written
-      if (F.kv && nn >= F.kv_col0 && (int64_t)kv_t * F.kv_ld < F.kv_bstride)
-        reinterpret_cast<TE*>(F.kv)[(int64_t)m * F.kv_bstride + (int64_t)kv_t * F.kv_ld + (nn - F.kv_col0)] = (TE)y;
-      if (F.emit_mel && em_t < F.emit_tmax) {
-        if (nn < F.emit_nmels) {
-          // frames after an utterance's stop are zero (its post-net then sees zero padding at
-          // its own length; this step's stop update is e + 1 > em_t, so no race on the read)
-          const float ym = (F.emit_stop_len && F.emit_stop_len[m] <= em_t) ? 0.f : y;
-          F.emit_mel[((int64_t)m * F.emit_tmax + em_t) * F.emit_nmels + nn] = ym;
-          reinterpret_cast<TE*>(F.emit_prev)[(int64_t)m * F.emit_nmels + nn] = (TE)ym;
-        } else if (nn == F.emit_nmels) {
-          // the stop logit (+ an injected per-utterance bias); the first frame at or above the
-          // threshold fixes the utterance's length (one thread owns row m's stop column)
-          const float ys = F.emit_stop_bias ? y + F.emit_stop_bias[(int64_t)m * F.emit_tmax + em_t] : y;
-          F.emit_stop[(int64_t)m * F.emit_tmax + em_t] = ys;
-          if (F.emit_stop_len && ys >= F.emit_stop_thr && F.emit_stop_len[m] > em_t) F.emit_stop_len[m] = em_t + 1;
-        }
-      }
-    }
-  }
-  if (F.emit_mel) {
-    // every workgroup has read the step counter (it addressed its stores with it): the
-    // last one to arrive advances it (and the dropout seed) and re-arms the counter
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      const int prev = __hip_atomic_fetch_add(F.emit_done, 1, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
-      if (prev == (int)gridDim.x - 1) {
-        *F.emit_done = 0;
-        if (em_t < F.emit_tmax) {   // the counter saturates at t_max (replays past it emit nothing)
-          *F.emit_t = em_t + 1;
-          if (F.emit_seed) *F.emit_seed += 1u;
-        }
-      }
-    }
-  }
-}
-
-// =====================================================================================
-// The decode step's FFN sublayer in one launch (tt2_ffn_decode): y = LN3(x + b2 + relu(x W1^T
-// + b1) W2^T) for m <= 64 rows, d = 512, F = 2048, with the arithmetic of the three launches
-// it replaces (skinny FFN1 with relu, skinny FFN2 split-K into 8 f32 slabs, tt2_ln_combine):
-// bit-identical.  One grid of 256 work groups; work group w takes split s = w / 32 (hidden
-// units 256 s .. + 255) and output column block c = w % 32 (columns 16 c .. + 15):
-//  (0) every lane issues its W2 chunks first (they do not depend on phase 1);
-//  (1) c < 16: hidden columns 256 s + 16 c .. + 15 -- the skinny FFN1 body (4 waves split
-//      K = 512, NCH 4) -- relu(. + b1) stored to `hidden`, then count[s] += 1;
-//  (2) every work group waits for count[s] == 16 (the producers of its K slice), then runs the
-//      skinny split-K body (NCH 2) on hidden[:, 256 s ..] and stores its slab columns,
-//      done[s] += 1;
-//  (3) work groups 0 .. m/4 - 1 wait for done[0..7] == 32 and combine one row per wave
-//      (ln_combine_vals<8>, as tt2_ln_combine).
-// A work group only ever waits for work groups of lower index (and the phase-3 ones, at most
-// 16, for all), so in-order dispatch makes progress even when the grid is not resident at once.
-// Cross-XCD visibility without cache maintenance: the hidden row and the slabs are stored
-// with agent-coherent (sc1, L2 write-through) stores, every wave waits for its stores'
-// acknowledgements before the work group's barrier and counter increment, and the readers
-// load them with sc1 buffer loads, which do not hit a stale L2 / L1 line.  (Agent-scope fences
-// instead -- an L2 write-back per producer and an L2 invalidate per waiter, 32 of each per XCD
-// per phase -- made the launch 2x slower than the three launches it replaces.)  The last
-// work group to leave re-arms the counters for the next launch.  A spin gives up after
-// FFN_SPIN_TICKS of the 100 MHz wall clock and raises sync[FFN_ERR].
-// Measured (tools/ffn_decode_ab.py, per-work-group stamps): each hand-off -- the producers'
-// stores acknowledged, the counter increment, the waiter's poll seeing it -- costs 1.3-2.3 us,
-// about what a launch boundary inside a graph costs, so the launch is 0.6-1.2 us SLOWER than
-// the three it replaces (10.9-11.3 vs 10.3 us per layer at m = 32).  Opt-in (decode schedule 4).
-// =====================================================================================
-constexpr int FFN_D = 512, FFN_F = 2048, FFN_WG = 256;
-constexpr uint64_t FFN_SPIN_TICKS = 2000000;   // 20 ms
-// counter i at sync[64 i] (256 B apart): count[s] (16 producers each), done[s] (the 32 slab
-// writers of split s: one counter per split, since 256 increments of one word serialise at its
-// atomic unit for ~3.5 us), exit, err
-enum { FFN_LINE = 64, FFN_DONE = 8, FFN_EXIT = 16, FFN_ERR = 17, FFN_NCTR = 18 };
-static_assert(FFN_NCTR * FFN_LINE <= TT2_FFN_SYNC_INTS && FFN_ERR * FFN_LINE == TT2_FFN_SYNC_ERR, "sync words");
-// how a phase's data reaches the next phase's readers (measurement builds): 0 sc1 stores and
-// sc1 loads; 1 plain stores, an agent-scope release (L2 write-back) per producer, sc1 loads;
-// 2 plain stores and loads, no cache maintenance (WRONG results across XCDs: timing floor only)
-#ifndef FFN_SYNC
-#define FFN_SYNC 0
-#endif
-#ifndef FFN_SLEEP
-#define FFN_SLEEP 1
-#endif
-
-template <typename TE> struct FfnArgs {
-  const TE* x; const TE* w1; const float* b1; const TE* w2; const float* b2;
-  const float* gamma; const float* beta;
-  TE* hid; float* slab; int32_t* sync; TE* y;
-  int M;
-  float eps;
-  uint64_t* stamps;   // optional [256][8] wall-clock stamps per work group (tt2_ffn_decode_stamps)
-};
-#define FFN_STAMP(k) \
-  if (a.stamps && threadIdx.x == 0) a.stamps[blockIdx.x * 8 + (k)] = wall_clock64()
-
-// every wave: its sc1 stores acknowledged, then the work group's barrier; thread 0 counts
-TT2_DEV void ffn_arrive(int32_t* ctr) {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");   // keeps the stores above (compiler)
-  __builtin_amdgcn_s_waitcnt(0);                            // vmcnt(0): this wave's stores done
-  __syncthreads();
-  if (threadIdx.x == 0) {
-#if FFN_SYNC == 1
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-#endif
-    __hip_atomic_fetch_add(ctr, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
-}
-template <typename T> TT2_DEV void ffn_st(T* p, T v) {
-#if FFN_SYNC == 0
-  typedef __attribute__((ext_vector_type(1))) unsigned short u16v;
-  if constexpr (sizeof(T) == 2)
-    __hip_atomic_store(reinterpret_cast<uint16_t*>(p), __builtin_bit_cast(uint16_t, v), __ATOMIC_RELAXED,
-                       __HIP_MEMORY_SCOPE_AGENT);
-  else
-    __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#else
-  *p = v;
-#endif
-}
-// 16-B agent-coherent load (sc1) of p (16-B aligned, within 2 GB of base)
-TT2_DEV uint4 ld_sc1(__amdgpu_buffer_rsrc_t rs, const void* base, const void* p) {
-  const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(
-      rs, (int)(reinterpret_cast<const char*>(p) - reinterpret_cast<const char*>(base)), 0, FFN_SYNC == 2 ? 0 : 16);
-  return make_uint4(v[0], v[1], v[2], v[3]);
-}
-TT2_DEV __amdgpu_buffer_rsrc_t ffn_rsrc(const void* base) {
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), (short)0, 0x7fffffff, 0x00020000);
-}
-// thread 0; the work group's barrier follows.  Waits until ctr[i * FFN_LINE] >= target for
-// i < n; the clock and the error word are checked every 16th poll only (a poll is one
-// agent-coherent load round trip)
-TT2_DEV void ffn_wait(int32_t* ctr, int n, int target, int32_t* err) {
-  const uint64_t t0 = wall_clock64();
-  for (int it = 1;; ++it) {
-    int lo = target;   // every counter's load in flight at once
-    for (int i = 0; i < n; ++i)
-      lo = min(lo, __hip_atomic_load(ctr + i * FFN_LINE, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-    if (lo >= target) break;
-    if ((it & 15) == 0) {
-      if (__hip_atomic_load(err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) break;
-      if (wall_clock64() - t0 > FFN_SPIN_TICKS) {
-        __hip_atomic_store(err, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        break;
-      }
-    }
-    __builtin_amdgcn_s_sleep(FFN_SLEEP);
-  }
-}
-
-template <typename TE, int MR>
-__global__ __launch_bounds__(NT) void ffn_decode_kernel(FfnArgs<TE> a) {
-  typedef typename SkT<TE>::V V8;
-  union U { uint4 u; V8 v; };
-  __shared__ float red[4][16 * MR][SK_COLS + 1];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, r = lane & 15, g = lane >> 4;
-  const int s = blockIdx.x >> 5, c = blockIdx.x & 31;
-  const int ecol = threadIdx.x & 15, erow = threadIdx.x >> 4;
-  const int M = a.M;
-  FFN_STAMP(0);
-  const TE* xr[MR];
-  const TE* hr[MR];
-  bool rok[MR];
-#pragma unroll
-  for (int q = 0; q < MR; ++q) {
-    rok[q] = 16 * q + r < M;
-    xr[q] = a.x + (int64_t)(rok[q] ? 16 * q + r : 0) * FFN_D;
-    hr[q] = a.hid + (int64_t)(rok[q] ? 16 * q + r : 0) * FFN_F;
-  }
-  // (0) phase 2's W2 slice: output column 16 c + r, k = 256 s + 64 wave + 32 cc + 8 g
-  const int k2 = s * 256 + wave * 64 + 8 * g;
-  U w2[2];
-  {
-    const TE* wrow = a.w2 + (int64_t)(c * SK_COLS + r) * FFN_F + k2;
-#pragma unroll
-    for (int cc = 0; cc < 2; ++cc) w2[cc].u = *reinterpret_cast<const uint4*>(wrow + 32 * cc);
-  }
-  if (c < 16) {
-    // (1) hidden column 256 s + 16 c + r, k = 128 wave + 32 cc + 8 g
-    const int n1 = s * 256 + c * SK_COLS;
-    const int k1 = wave * 128 + 8 * g;
-    U w1[4], a1[MR][4];
-    const TE* wrow = a.w1 + (int64_t)(n1 + r) * FFN_D + k1;
-#pragma unroll
-    for (int cc = 0; cc < 4; ++cc) w1[cc].u = *reinterpret_cast<const uint4*>(wrow + 32 * cc);
-#pragma unroll
-    for (int cc = 0; cc < 4; ++cc)
-#pragma unroll
-      for (int q = 0; q < MR; ++q)
-        a1[q][cc].u = *reinterpret_cast<const uint4*>(rok[q] ? (const void*)(xr[q] + k1 + 32 * cc)
-                                                              : (const void*)g_zero_page);
-    const float e_bias = a.b1[n1 + ecol];
-    __builtin_amdgcn_sched_barrier(0);
-    f32x4 acc[MR];
-#pragma unroll
-    for (int q = 0; q < MR; ++q) acc[q] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int cc = 0; cc < 4; ++cc)
-#pragma unroll
-      for (int q = 0; q < MR; ++q) acc[q] = SkT<TE>::mma(a1[q][cc].v, w1[cc].v, acc[q]);
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-      for (int q = 0; q < MR; ++q) red[wave][16 * q + 4 * g + i][r] = acc[q][i];
-    __syncthreads();
-#pragma unroll
-    for (int hrow = 0; hrow < MR; ++hrow) {
-      const int m = erow + 16 * hrow;
-      if (m < M) {
-        // the skinny epilogue's expression: relu(alpha v + bias + residual 0) + pe 0, alpha 1
-        const float v = (red[0][m][ecol] + red[1][m][ecol]) + (red[2][m][ecol] + red[3][m][ecol]);
-        float y = 1.f * v + e_bias + 0.f;
-        y = fmaxf(y * 1.f, 0.f);
-        y += 0.f;
-        ffn_st(a.hid + (int64_t)m * FFN_F + n1 + ecol, (TE)y);
-      }
-    }
-    FFN_STAMP(1);
-    ffn_arrive(a.sync + FFN_LINE * s);
-    FFN_STAMP(2);
-  }
-  // (2) the K slice 256 s .. + 255 of hidden once its 16 producers are done
-  if (threadIdx.x == 0) ffn_wait(a.sync + FFN_LINE * s, 1, 16, a.sync + FFN_LINE * FFN_ERR);
-  __syncthreads();
-  FFN_STAMP(3);
-  {
-    const __amdgpu_buffer_rsrc_t hrs = ffn_rsrc(a.hid);
-    U a2[MR][2];
-#pragma unroll
-    for (int cc = 0; cc < 2; ++cc)
-#pragma unroll
-      for (int q = 0; q < MR; ++q)   // rows past m read row 0 and are not stored
-        a2[q][cc].u = ld_sc1(hrs, a.hid, hr[q] + k2 + 32 * cc);
-    f32x4 acc[MR];
-#pragma unroll
-    for (int q = 0; q < MR; ++q) acc[q] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int cc = 0; cc < 2; ++cc)
-#pragma unroll
-      for (int q = 0; q < MR; ++q) acc[q] = SkT<TE>::mma(a2[q][cc].v, w2[cc].v, acc[q]);
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-      for (int q = 0; q < MR; ++q) red[wave][16 * q + 4 * g + i][r] = acc[q][i];
-    __syncthreads();
-#pragma unroll
-    for (int hrow = 0; hrow < MR; ++hrow) {
-      const int m = erow + 16 * hrow;
-      if (m < M)
-        ffn_st(a.slab + ((int64_t)s * M + m) * FFN_D + c * SK_COLS + ecol,
-               (red[0][m][ecol] + red[1][m][ecol]) + (red[2][m][ecol] + red[3][m][ecol]));
-    }
-    FFN_STAMP(4);
-    ffn_arrive(a.sync + FFN_LINE * (FFN_DONE + s));
-    FFN_STAMP(5);
-  }
-  // (3) one row per wave once every slab is written
-  if ((int)blockIdx.x < (M + 3) / 4) {
-    if (threadIdx.x == 0) ffn_wait(a.sync + FFN_LINE * FFN_DONE, 8, 32, a.sync + FFN_LINE * FFN_ERR);
-    __syncthreads();
-    FFN_STAMP(6);
-    const int row = blockIdx.x * 4 + wave;
-    if (row < M) {
-      // ln_combine_row<8> with the slabs read agent-coherently
-      const __amdgpu_buffer_rsrc_t srs = ffn_rsrc(a.slab);
-      const int c0 = lane * 8;
-      float v[8], p[8][8], bb[8], gm[8], be[8], o[8];
-      ld8f(a.x + (int64_t)row * FFN_D + c0, v);
-#pragma unroll
-      for (int sl = 0; sl < 8; ++sl) {
-        const float* ps = a.slab + ((int64_t)sl * M + row) * FFN_D + c0;
-        const uint4 u0 = ld_sc1(srs, a.slab, ps), u1 = ld_sc1(srs, a.slab, ps + 4);
-        p[sl][0] = __uint_as_float(u0.x); p[sl][1] = __uint_as_float(u0.y);
-        p[sl][2] = __uint_as_float(u0.z); p[sl][3] = __uint_as_float(u0.w);
-        p[sl][4] = __uint_as_float(u1.x); p[sl][5] = __uint_as_float(u1.y);
-        p[sl][6] = __uint_as_float(u1.z); p[sl][7] = __uint_as_float(u1.w);
-      }
-      ld8f(a.b2 + c0, bb);
-      ld8f(a.gamma + c0, gm);
-      ld8f(a.beta + c0, be);
-      ln_combine_vals<8>(v, p, bb, gm, be, a.eps, o);
-      typedef TE t8 __attribute__((ext_vector_type(8)));
-      t8 yv;
-#pragma unroll
-      for (int j = 0; j < 8; ++j) yv[j] = (TE)o[j];
-      *reinterpret_cast<t8*>(a.y + (int64_t)row * FFN_D + lane * 8) = yv;
-    }
-  }
-  // every wait of this work group is behind it: the last one out re-arms the counters
-  FFN_STAMP(7);
-  if (threadIdx.x == 0) {
-    const int prev =
-        __hip_atomic_fetch_add(a.sync + FFN_LINE * FFN_EXIT, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (prev == FFN_WG - 1) {
-#pragma unroll
-      for (int i = 0; i < FFN_ERR; ++i)
-        __hip_atomic_store(a.sync + FFN_LINE * i, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-  }
-}
-
-template <bool AK, bool BKC>
-hipError_t launch2(const OpDesc& A, const OpDesc& B, const EpiParams& E, int M, int N, int K, int splits, float* ws,
-                   hipStream_t s) {
-  int k_split = K;
-  if (splits > 1) {
-    k_split = ((K + splits - 1) / splits + BK2 - 1) / BK2 * BK2;
-    splits = (K + k_split - 1) / k_split;
-  }
-  const int ntm = (M + BM - 1) / BM, ntn = (N + BN - 1) / BN;
-  dim3 grid(ntm * ntn, splits);
-  ProbeScope ps(s, 0);   // no span record in this kernel
-  if (ps.ext())
-    hipExtLaunchKernelGGL((gemm2_kernel<AK, BKC>), grid, dim3(NT), 0, s, ps.e0, ps.e1, 0, A, B, E, M, N, K, k_split,
-                     splits > 1 ? ws : nullptr, ntm, ntn);
-  else
-    hipLaunchKernelGGL((gemm2_kernel<AK, BKC>), grid, dim3(NT), 0, s, A, B, E, M, N, K, k_split,
-                     splits > 1 ? ws : nullptr, ntm, ntn);
-  if (splits > 1 && !E.main_only)
-    hipLaunchKernelGGL(gemm_splitk_reduce, dim3(splitk_blocks(M, N, E)), dim3(256), 0, s, ws, splits, E, M, N);
-  return hipGetLastError();
-}
-
-
-// Fragment reads of the 256-row LDS images: K-contiguous [rows][8 chunks] with chunk c of
-// row r at c ^ (r & 7); M/N-contiguous as 128-column sub-images [64 k][16 chunks] with
-// chunk c of row k at c ^ mc_swz(k) (v2's images, stacked).
-template <bool KC>
-TT2_DEV void g7_frag(Frag8<bf16>& f, const char* img, int r0, int kk, int lane) {
-  if (KC) frag2<true>(f, img, r0, kk, lane);
-  else frag2<false>(f, img + (r0 >> 7) * 16384, r0 & 127, kk, lane);
-}
-
-// Measurement hook: tools/gemm_stamps.hip defines these (and the buffer they write)
-// before including this file; the library build compiles them away.  The in-step phase
-// build (-DTT2_PHASE=1, tools/g7_phases.py) writes them into the launch probe's per-work-group
-// record (TT2_SPAN_W slots, layout at span_begin): s_memtime of MFMA wave 0 at the start of
-// K steps 0..11 and after their MFMAs, and at the epilogue's four points.
-#if defined(TT2_PHASE) && !defined(G7_STAMP)
-#define G7_STAMP(t, slot)                                                                  \
-  if (srec && threadIdx.x == 0) {                                                          \
-    const int si_ = (t) == nkt ? 27 + (slot) : (t) < 12 ? 3 + 2 * (t) + (slot) : -1;        \
-    if (si_ >= 0) srec[si_] = __builtin_amdgcn_s_memtime();                                \
-  }
-#endif
-#ifndef G7_STAMP
-#define G7_STAMP(t, slot)
-#endif
-#ifndef G7_RT
-#define G7_RT(slot)
-#endif
-
-// =====================================================================================
-// v7 (bf16, plain operands): warp-specialised 256 x 128 tile.  In v6 every wave both
-// issues LDS-DMA copies and multiplies; an LDS-DMA issue stalls its wave while the
-// CU's address path (~64 B/clk) drains, so the MFMA stream of all 8 waves stops for
-// ~700 cycles per K step (in-kernel s_memtime timeline).  Here 4 loader waves (one per
-// SIMD) do nothing but copy, three K steps deep into a 3-stage ring, and 8 MFMA waves
-// (4 M x 2 N, 64 x 64 each) only read fragments and multiply; one s_barrier per step
-// hands stages over (loaders wait their copies of step t+1 with a counted vmcnt first).
-// The MFMA operands are swapped (D = B A^T: each lane holds 4 consecutive C columns of
-// one row) and v_permlane16_swap pairs adjacent column blocks, so every lane stores 8
-// consecutive columns of a row straight from registers -- no LDS round trip for C.
-// ksum (row sums of an M-contiguous A): the wn == 0 waves multiply their A fragments by an
-// all-ones fragment (one extra MFMA each).
-// =====================================================================================
 #ifndef TT2_G10_AUTO
 #define TT2_G10_AUTO 1
 #endif
@@ -1281,1563 +28,6 @@ TT2_DEV void g7_frag(Frag8<bf16>& f, const char* img, int r0, int kk, int lane) 
 #ifndef G11_MAX_K       // ... up to this K (one MFMA wave per SIMD loses to v7's two at long K:
 #define G11_MAX_K 1024  // 12800 x 512 x 2048 30.3 -> 30.9 us; K = 512: -7 %)
 #endif
-#ifndef G7_BUF   // plain operands' LDS-DMA copies as buffer_load ... lds (1) or global_load_lds (0)
-#define G7_BUF 1
-#endif
-#ifndef G7_PRIO   // MFMA waves 4-7 (the younger of each SIMD's two) at s_setprio 1 for the K loop:
-#define G7_PRIO 0   // bit-identical, within +-2 % per GEMM, the step the same (profiles/r06_g7_prio_ab.txt)
-#endif
-#ifndef G7_REG   // the loader waves stage plain operand steps through VGPRs (1) or by LDS-DMA (0):
-#define G7_REG 0   // bit-identical, 3-17 % slower per GEMM, step 6.58 -> 6.88 ms
-#endif
-constexpr int G7_NT = 768;                          // 8 MFMA waves + 4 loader waves
-constexpr int G7_A = 256 * 128, G7_B = 128 * 128;   // bytes per stage: 64 k x 2 B per row
-constexpr int G7_STAGE = G7_A + G7_B;               // 48 KB
-constexpr int G7_STAGES = 3;
-constexpr int G7_AI = G7_A / 1024 / 4, G7_BI = G7_B / 1024 / 4;   // copies per loader wave: 8 + 4
-constexpr int G7_SMEM = G7_STAGES * G7_STAGE;
-
-// Loader-lane state of one operand (NI copies per step).  Plain operands: a loop-
-// invariant byte offset from a wave-uniform base.  Conv operands (implicit im2col,
-// ld = C, element (outer, inner) at (outer + tap - pad) * C + ci) also track the
-// copy's conv coordinates incrementally (64 k per step, C >= 64 and T >= 64 so one
-// conditional wrap suffices): K-contiguous A (k = tap * C + ci): tap and ci of the
-// chunk, t of the row; M/N-contiguous B (k = token row): t of the k row, tap of the
-// column.  A copy reads the zero page when its chunk is conv padding or k >= ke.
-template <int NI> struct G7Lane {
-  uint32_t off[NI];
-  int t[NI], tap[NI], ci[NI];
-  uint32_t vm[NI];   // K-contiguous conv operand with C % 64 == 0: bit tap = row t + tap - pad is inside [0, T)
-};
-
-// A K-contiguous conv operand whose channel count is a multiple of 64 keeps every 64-deep K
-// step inside one tap, so a copy's validity is one bit of a per-row tap mask (no per-step
-// coordinate tracking on the loader waves, whose VALU work slows the MFMA waves' K loop).
-TT2_DEV bool g7_conv_fast(const OpDesc& d) { return d.conv_t > 0 && (d.conv_c & 63) == 0; }
-
-template <bool KC, int NI>
-TT2_DEV void g7_lane_init(G7Lane<NI>& L, const OpDesc& d, int r0, int kb, int lane, int lw) {
-#pragma unroll
-  for (int i = 0; i < NI; ++i) {
-    const int inst = lw * NI + i;
-    if (KC) {
-      const int row = inst * 8 + (lane >> 3);
-      const int gc = (lane & 7) ^ (row & 7);
-      const int r = min(r0 + row, d.outer_max - 1);
-      L.off[i] = (uint32_t)(((int64_t)r * d.ld + gc * 8) * 2);
-      if (d.conv_t > 0) {
-        const int k = kb + gc * 8;
-        L.t[i] = r % d.conv_t;
-        L.tap[i] = k / d.conv_c;
-        L.ci[i] = k - L.tap[i] * d.conv_c;
-        const int lo = max(0, d.conv_pad - L.t[i]), hi = min(31, d.conv_t - 1 - L.t[i] + d.conv_pad);
-        L.vm[i] = hi >= lo ? (0xFFFFFFFFu >> (31 - hi)) & (0xFFFFFFFFu << lo) : 0u;   // taps lo..hi
-      }
-    } else {
-      const int sub = inst >> 4, kr = (inst & 15) * 4 + (lane >> 4);
-      const int gc = (lane & 15) ^ mc_swz(kr);
-      int col = r0 + sub * 128 + gc * 8;
-      col = col < d.inner_max ? col : d.inner_max - 8;
-      L.off[i] = (uint32_t)(((int64_t)kr * d.ld + col) * 2);
-      if (d.conv_t > 0) {
-        L.t[i] = (kb + kr) % d.conv_t;
-        L.tap[i] = col / d.conv_c;
-        L.ci[i] = 0;
-      }
-    }
-  }
-}
-
-template <bool KC, int NI>
-TT2_DEV void g7_issue(const OpDesc& d, G7Lane<NI>& L, char* lds, int k0, int ke, int lane, int lw, bool tl,
-                      bool cfast) {
-  const bool conv = d.conv_t > 0;
-  const int64_t shift = conv ? (int64_t)d.conv_pad * d.conv_c : 0;
-  const char* base = reinterpret_cast<const char*>(d.p) + ((KC ? (int64_t)k0 : (int64_t)k0 * d.ld) - shift) * 2;
-  if (!conv && !tl) {
-#if G7_BUF && defined(__HIP_DEVICE_COMPILE__)   // (the host pass has no buffer_load_lds builtin)
-    // buffer_load ... lds: the step's byte offset in an SGPR, the lane's loop-invariant offset in
-    // one VGPR (no 64-bit lane address per copy); operands < 2 GB (the plan's v7 condition)
-    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(d.p), (short)0, 0x7fffffff,
-                                                                        0x00020000);
-    const unsigned soff = (unsigned)((KC ? (int64_t)k0 : (int64_t)k0 * d.ld) * 2);
-#pragma unroll
-    for (int i = 0; i < NI; ++i)
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lvoid_t*)(lds + (lw * NI + i) * 1024), 16, L.off[i], soff, 0, 0);
-#else
-#pragma unroll
-    for (int i = 0; i < NI; ++i)
-      __builtin_amdgcn_global_load_lds((gvoid_t*)(base + L.off[i]), (lvoid_t*)(lds + (lw * NI + i) * 1024), 16, 0,
-                                       0);
-#endif
-    return;
-  }
-  if (KC && cfast) {   // the whole step reads tap k0 / C
-    const int tap = k0 / d.conv_c;
-#pragma unroll
-    for (int i = 0; i < NI; ++i) {
-      const void* src = (L.vm[i] >> tap) & 1u ? (const void*)(base + L.off[i]) : (const void*)g_zero_page;
-      __builtin_amdgcn_global_load_lds((gvoid_t*)src, (lvoid_t*)(lds + (lw * NI + i) * 1024), 16, 0, 0);
-    }
-    return;
-  }
-#pragma unroll
-  for (int i = 0; i < NI; ++i) {
-    const int inst = lw * NI + i;
-    int k;
-    if (KC) {
-      const int row = inst * 8 + (lane >> 3);
-      k = k0 + ((lane & 7) ^ (row & 7)) * 8;
-    } else {
-      k = k0 + (inst & 15) * 4 + (lane >> 4);
-    }
-    bool ok = k < ke;
-    if (conv) {
-      ok = ok && (unsigned)(L.t[i] + L.tap[i] - d.conv_pad) < (unsigned)d.conv_t;
-      if (KC) {   // next step: k += 64 within (tap, ci)
-        L.ci[i] += 64;
-        if (L.ci[i] >= d.conv_c) { L.ci[i] -= d.conv_c; ++L.tap[i]; }
-      } else {    // next step: token row += 64
-        L.t[i] += 64;
-        if (L.t[i] >= d.conv_t) L.t[i] -= d.conv_t;
-      }
-    }
-    const void* src = ok ? (const void*)(base + L.off[i]) : (const void*)g_zero_page;
-    __builtin_amdgcn_global_load_lds((gvoid_t*)src, (lvoid_t*)(lds + inst * 1024), 16, 0, 0);
-  }
-}
-
-// Register-staged copies into their ring slots (the LDS image LDS-DMA would have written).
-template <int NI>
-TT2_DEV void g7_put(const u32x4 (&r)[NI], char* lds, int lane, int lw) {
-#pragma unroll
-  for (int i = 0; i < NI; ++i) *reinterpret_cast<u32x4*>(lds + (lw * NI + i) * 1024 + lane * 16) = r[i];
-}
-
-// One GEMM problem of a (possibly grouped) v7 launch.  Work item = (split, tile).
-struct G7Prob {
-  OpDesc A, B;
-  EpiParams E;
-  int M, N, K, k_split, splits, ntn, items, item0;
-  float* ws;   // split-K slabs [splits][M][N] (+ [splits][M] k-sums); used when splits > 1
-  int lds_epi; // C leaves through an LDS image in whole 256-B row segments (bf16 C, no split)
-  int pre_x;     // the loader waves stage the bf16 residual (1) or gate (2) tile in LDS (lds_epi only)
-  int epi_fast;  // straight-line image epilogue for this option set (g7_epi_fast), -1: general path
-  unsigned long long* span;   // launch probe's span record (grouped launch: p[0]'s), else null
-};
-constexpr int G7_MAXP = 8;
-// A deferred LayerNorm backward's column-sum finalize (tt2_ln_args with defer_finalize) that
-// rides in the group's split-K reduce launch: part[nb][3][C] -> dg / db / dd (each
-// = gb * old + sum when gb != 0), one wave per output column, fixed order.
-struct G7Fin {
-  const float* part;
-  float* dst[3];
-  float gb;
-  int nb, C;
-};
-struct G7Group {
-  G7Prob p[G7_MAXP];
-  int np, items;
-  int ibase;   // first item of this launch (a capped grid: several launches)
-  G7Fin fin;   // nb == 0: none
-  int fin_only;   // the reduce launch holds only the finalize plane (no split problem to reduce)
-};
-constexpr int G7_FIN_WAVES = 4;   // columns per 256-thread reduce block
-
-// The epilogue's 256-row image (C, and before it the staged residual / gate in place):
-// rows 0..191 fill the ring stage of K step nkt - 3 (the first stage that no later step
-// reuses), rows 192..255 the stage of step nkt - 2, so the staged tile can land while the
-// last K steps still read the third stage.  Chunk c of row r sits at slot c ^ (r & 15).
-TT2_DEV int g7_img_row(int nkt, int r) {
-  return r < 192 ? (nkt % 3) * G7_STAGE + r * 256 : ((nkt + 1) % 3) * G7_STAGE + (r - 192) * 256;
-}
-
-TT2_DEV void bf16x8_unpack(const u32x4& v, float (&f)[8]) {
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    f[2 * j] = __uint_as_float(v[j] << 16);
-    f[2 * j + 1] = __uint_as_float(v[j] & 0xffff0000u);
-  }
-}
-
-// whole-row store of the LDS C image (all 768 threads; 4 rows x 256 B per wave instruction).
-// Nontemporal: C streams out during the epilogue instead of sitting dirty in L2 until the
-// end-of-kernel write-back (the consumer kernel reads it from the Infinity Cache either way).
-// With E.cstats (a BatchNorm's statistics fused into the producing GEMM), the stored values'
-// column moments over the tile's rows ride along: every thread keeps one 8-column chunk
-// (768 % 16 == 0) and sums (v - k), (v - k)^2 over its rows with k = the tile's row 0 (the
-// statistics kernel's shift), the 4 lanes of a chunk in a wave combine by shuffles, the 12 waves
-// through the free ring stage, and 128 threads write the chunk's mean and M2 per column.
-// With E.bnb.part (the BatchNorm backward's statistics pass fused into the GEMM that produces its
-// dout), each thread sums, over the same rows and chunk, dpre = dout * keep * act'(z) and
-// dpre * xhat exactly as bn_bwd_stats_kernel forms them per element (its y rows are loaded
-// before the store loop, all in flight), then the same reduction writes plain chunk sums.
-// SM (compile time, so the plain kernels carry none of it): 0 store only, 1 col_stats, 2 bn_bwd sums.
-template <int SM>
-TT2_DEV void g7_store_c(const G7Prob& P, char* smem, int m0, int n0, int nkt) {
-  bf16* C = reinterpret_cast<bf16*>(P.E.c);
-  constexpr bool st = SM == 1, sb = SM == 2;
-  const int c = threadIdx.x & 15;
-  float k[8], s1[8], s2[8];
-  if (st) bf16x8_unpack(*reinterpret_cast<const u32x4*>(smem + g7_img_row(nkt, 0) + (c << 4)), k);
-#pragma unroll
-  for (int j = 0; j < 8; ++j) s1[j] = s2[j] = 0.f;
-  constexpr int NR = (256 * 16 + G7_NT - 1) / G7_NT;   // rows per thread (6; the last only for some)
-  constexpr int YB = NR / 2;   // y rows in flight per batch (two batches: register pressure)
-  u32x4 yv[YB];
-  float mu[8], rs[8], ga[8], be[8];
-  uint32_t seed = 0;
-  auto load_y = [&](int i0) {
-#pragma unroll
-    for (int i = 0; i < YB; ++i) {
-      const int r = (threadIdx.x >> 4) + (G7_NT / 16) * (i0 + i), m = min(m0 + r, P.M - 1);
-      yv[i] = r < 256 ? *reinterpret_cast<const u32x4*>(P.E.bnb.y + (int64_t)m * P.N + n0 + 8 * c)
-                      : u32x4{0, 0, 0, 0};
-    }
-  };
-  if constexpr (sb) {
-    const int n = n0 + 8 * c;
-    load_y(0);
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      mu[j] = P.E.bnb.mean[n + j]; rs[j] = P.E.bnb.rstd[n + j];
-      ga[j] = P.E.bnb.gamma[n + j]; be[j] = P.E.bnb.beta[n + j];
-    }
-    seed = P.E.bnb.drop.thr ? *P.E.bnb.drop.seed : 0u;
-  }
-#pragma unroll
-  for (int i = 0; i < NR; ++i) {
-    if constexpr (sb) {
-      if (i == YB) load_y(YB);
-    }
-    const int id = threadIdx.x + G7_NT * i;
-    if (id >= 256 * 16) break;
-    const int r = id >> 4, m = m0 + r, n = n0 + 8 * c;
-    if (m < P.M && n < P.N) {
-      const u32x4 v = *reinterpret_cast<const u32x4*>(smem + g7_img_row(nkt, r) + ((c ^ (r & 15)) << 4));
-      u32x4* dst = reinterpret_cast<u32x4*>(C + (int64_t)m * P.E.ldc + n);
-      __builtin_nontemporal_store(v, dst);
-      if constexpr (st) {
-        float f[8];
-        bf16x8_unpack(v, f);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-          const float d = f[j] - k[j];
-          s1[j] += d;
-          s2[j] += d * d;
-        }
-      }
-      if constexpr (sb) {
-        float d[8], yf[8];
-        bf16x8_unpack(v, d);
-        bf16x8_unpack(yv[i % YB], yf);
-        const DropDesc& dd = P.E.bnb.drop;
-        const uint32_t bits = dd.thr ? drop_bits8(seed, dd.site, (uint32_t)((int64_t)m * P.N + n), dd.thr) : 0xFFu;
-        const float sc = dd.thr ? dd.scale : 1.f;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-          const float keep = (bits >> j) & 1u ? sc : 0.f;
-          const float xh = (yf[j] - mu[j]) * rs[j];
-          const float z = act_f(P.E.bnb.act, xh * ga[j] + be[j]);
-          const float dp = d[j] * keep * act_grad_from_out(P.E.bnb.act, z);
-          s1[j] += dp;
-          s2[j] += dp * xh;
-        }
-      }
-    }
-  }
-  if constexpr (!st && !sb) return;
-  else {
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {   // lanes c, c + 16, c + 32, c + 48 of the wave hold the same chunk
-    s1[j] += __shfl_xor(s1[j], 16);
-    s2[j] += __shfl_xor(s2[j], 16);
-    s1[j] += __shfl_xor(s1[j], 32);
-    s2[j] += __shfl_xor(s2[j], 32);
-  }
-  // the ring stage neither image part occupies (every K step's copies have landed)
-  float* red = reinterpret_cast<float*>(smem + ((nkt + 2) % 3) * G7_STAGE);   // [12 waves][128 cols][2]
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  if (lane < 16) {
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      red[(wave * 128 + 8 * c + j) * 2 + 0] = s1[j];
-      red[(wave * 128 + 8 * c + j) * 2 + 1] = s2[j];
-    }
-  }
-  __syncthreads();
-  const int t = threadIdx.x;
-  if (t < 128 && n0 + t < P.N) {
-    float S1 = 0.f, S2 = 0.f;
-    for (int w = 0; w < G7_NT / 64; ++w) {
-      S1 += red[(w * 128 + t) * 2 + 0];
-      S2 += red[(w * 128 + t) * 2 + 1];
-    }
-    const float kt = __uint_as_float((uint32_t)*reinterpret_cast<const uint16_t*>(smem + g7_img_row(nkt, 0) +
-                                                                                  2 * t) << 16);
-    if constexpr (st) {
-      const float nr = (float)min(256, P.M - m0);
-      float* out = P.E.cstats + (int64_t)(m0 / 256) * 2 * P.N + n0 + t;
-      out[0] = kt + S1 / nr;
-      out[P.N] = fmaxf(S2 - S1 * S1 / nr, 0.f);
-    } else {
-      float* out = P.E.bnb.part + (int64_t)(m0 / 256) * 2 * P.N + n0 + t;
-      out[0] = S1;
-      out[P.N] = S2;
-    }
-  }
-  }
-}
-
-// Loader waves: stage rows [r0, r0 + 4 * ni * 4) of the residual / gate tile (bf16, 16-B
-// aligned rows) into the image, ni copies per wave (rows past M repeat row M - 1).  The copies
-// are nontemporal (G7_X_AUX 2 = nt): each line is read once, and as default-policy lines they
-// pushed the B operand, which every row tile of the launch re-reads, out of the XCD's L2.
-#ifndef G7_X_AUX
-#define G7_X_AUX 2
-#endif
-TT2_DEV void g7_issue_x(const G7Prob& P, const void* x, int64_t ldx, char* smem, int nkt, int m0, int n0, int r0,
-                        int ni, int lane, int lw) {
-  const char* base = reinterpret_cast<const char*>(x);
-  for (int i = 0; i < ni; ++i) {
-    const int inst = lw * ni + i, r = r0 + inst * 4 + (lane >> 4);
-    const int m = min(m0 + r, P.M - 1), c = (lane & 15) ^ (r & 15);
-    __builtin_amdgcn_global_load_lds((gvoid_t*)(base + ((int64_t)m * ldx + n0 + 8 * c) * 2),
-                                     (lvoid_t*)(smem + g7_img_row(nkt, r0 + inst * 4)), 16, 0, G7_X_AUX);
-  }
-}
-
-// Straight-line LDS-image epilogue of a FULL tile for one option set, fixed at compile time:
-// the general path (epi_calc8 over run-time options, with per-lane bounds tests) compiles to
-// a long chain of branches that took ~5k cycles of the MFMA waves per tile (tools/gemm_stamps.hip),
-// as long as three K steps.  Same operations, same order (alpha, bias, residual, ReLU, gate,
-// dropout), so the results are bit-identical to the general path.  The dropout keep bits
-// (drop_bits8 of the lane's 8 groups of 8 columns, group 2 i + pr at bits 8 (2 i + pr)) were
-// hashed during the K loop, where the MFMA waves' VALU is otherwise idle.
-template <bool BIAS, bool RELU, bool DROP, int PX>
-TT2_DEV void g7_epi_fast(const EpiParams& E, const f32x4 (&acc)[4][4], const f32x4 (&pbias)[2][2], char* smem,
-                         int nkt, int m0, int n0, int wm, int wn, int lane, uint64_t dbits) {
-  const int q = lane >> 4;
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int r = wm * 64 + 16 * i + (lane & 15), m = m0 + r;
-#pragma unroll
-    for (int pr = 0; pr < 2; ++pr) {
-      float v[8];
-#pragma unroll
-      for (int rr = 0; rr < 4; ++rr) {
-        const auto sw = __builtin_amdgcn_permlane16_swap(__float_as_uint(acc[i][2 * pr][rr]),
-                                                         __float_as_uint(acc[i][2 * pr + 1][rr]), false, false);
-        v[rr] = __uint_as_float(sw[0]);
-        v[4 + rr] = __uint_as_float(sw[1]);
-      }
-      const int cl = wn * 64 + 16 * (2 * pr + (q & 1)) + 8 * (q >> 1), n = n0 + cl;
-      char* cp = smem + g7_img_row(nkt, r) + (((cl >> 3) ^ (r & 15)) << 4);
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        v[j] = BIAS ? v[j] * E.alpha + pbias[pr][0][j] : v[j] * E.alpha;
-        v[4 + j] = BIAS ? v[4 + j] * E.alpha + pbias[pr][1][j] : v[4 + j] * E.alpha;
-      }
-      if (PX) {
-        float t[8];
-        unpack_lds8(cp, t);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-          if (PX == 1) v[j] += t[j];
-          else v[j] = t[j] != 0.f ? v[j] * E.gate_scale : 0.f;
-        }
-      }
-      if (RELU) {
-#pragma unroll
-        for (int j = 0; j < 8; ++j) v[j] = fmaxf(v[j], 0.f);
-      }
-      if (DROP) {
-        const uint32_t kb = (uint32_t)(dbits >> (8 * (2 * i + pr)));
-#pragma unroll
-        for (int j = 0; j < 8; ++j) v[j] = (kb >> j) & 1u ? v[j] * E.drop.scale : 0.f;
-      }
-      bf16x8 x;
-#pragma unroll
-      for (int j = 0; j < 8; ++j) x[j] = (bf16)v[j];
-      *reinterpret_cast<bf16x8*>(cp) = x;
-    }
-  }
-}
-
-template <bool AK, bool BKC, int SM = 0>
-TT2_DEV void g7_item(const G7Prob& P, int tile, int split, char* smem, unsigned long long* span) {
-#ifdef TT2_PHASE
-  unsigned long long* srec = span ? span + TT2_SPAN_W * blockIdx.x : nullptr;
-#else
-  (void)span;
-#endif
-  const OpDesc& A = P.A;
-  const OpDesc& B = P.B;
-  const EpiParams& E = P.E;
-  const int M = P.M, N = P.N, K = P.K, ntn = P.ntn;
-  float* ws = P.splits > 1 ? P.ws : nullptr;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int m0 = (tile / ntn) * 256, n0 = (tile % ntn) * 128;
-  const int kb = split * P.k_split, ke = min(K, kb + P.k_split);
-  const int nkt = (ke - kb + 63) / 64;
-  const bool tail = ((ke - kb) & 63) != 0;
-  if (wave >= 8) {   // ------------------------------------------------ loader waves
-    const int lw = wave - 8;
-    // staged epilogue operand (whole tiles only)
-    const bool px = P.pre_x && n0 + 128 <= N;
-    const void* xs = P.pre_x == 1 ? E.res : E.gate;
-    const int64_t ldx = P.pre_x == 1 ? E.ldr : E.ldg;
-#if G7_REG
-    // Register-staged operand steps (G7_REG; plain operands, no K tail -- conv operands and
-    // tails keep the LDS-DMA ring below): the loader lanes load a step's 16-B pieces into VGPRs
-    // (global_load_dwordx4, 48 per lane) and write them into the ring slot with ds_write_b128
-    // once the slot is free: step t + 2 is written at the start of step t (into the stage step
-    // t - 1 released), then step t + 3 is loaded, so one step is in flight in VGPRs.
-    // The same bytes land at the same LDS addresses as the LDS-DMA copies (bit-identical
-    // results).  Measured slower than the LDS-DMA ring on every shape (tools/lib_ab.py, DESIGN.md
-    // 5.2): off by default, kept for the A/B.
-    if (A.conv_t == 0 && B.conv_t == 0 && !tail) {
-      // (lane state per path: the conv path's coordinates are not live here)
-      G7Lane<G7_AI> la;
-      G7Lane<G7_BI> lb;
-      g7_lane_init<AK>(la, A, m0, kb, lane, lw);
-      g7_lane_init<BKC>(lb, B, n0, kb, lane, lw);
-      u32x4 ra[G7_AI], rb[G7_BI];
-      auto fetch = [&](int step) {   // plain operands: loop-invariant lane offsets
-        const int k0 = kb + 64 * step;
-        const char* ba = reinterpret_cast<const char*>(A.p) + (AK ? (int64_t)k0 : (int64_t)k0 * A.ld) * 2;
-        const char* bb = reinterpret_cast<const char*>(B.p) + (BKC ? (int64_t)k0 : (int64_t)k0 * B.ld) * 2;
-#pragma unroll
-        for (int i = 0; i < G7_AI; ++i) ra[i] = *reinterpret_cast<const u32x4*>(ba + la.off[i]);
-#pragma unroll
-        for (int i = 0; i < G7_BI; ++i) rb[i] = *reinterpret_cast<const u32x4*>(bb + lb.off[i]);
-      };
-      auto put = [&](int stage) {
-        char* sa = smem + stage * G7_STAGE;
-        g7_put<G7_AI>(ra, sa, lane, lw);
-        g7_put<G7_BI>(rb, sa + G7_A, lane, lw);
-      };
-      fetch(0);
-      put(0);
-      if (nkt > 1) { fetch(1); put(1); }
-      if (nkt > 2) fetch(2);
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      __builtin_amdgcn_s_barrier();
-      int st = 2;
-      for (int t = 0; t < nkt; ++t) {
-        if (t + 2 < nkt) {
-          put(st);   // step t + 2 into the stage step t - 1 released
-          st = st == 2 ? 0 : st + 1;
-          if (t + 3 < nkt) fetch(t + 3);
-        } else if (px) {
-          if (t == nkt - 2 || nkt == 1) g7_issue_x(P, xs, ldx, smem, nkt, m0, n0, 0, 12, lane, lw);
-          if (t == nkt - 1) g7_issue_x(P, xs, ldx, smem, nkt, m0, n0, 192, 4, lane, lw);
-        }
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // this wave's slot writes are done
-        __builtin_amdgcn_s_barrier();
-      }
-    } else
-#endif
-    {
-    G7Lane<G7_AI> la;
-    G7Lane<G7_BI> lb;
-    const bool cfast_a = g7_conv_fast(A) && !tail, cfast_b = g7_conv_fast(B) && !tail;
-    g7_lane_init<AK>(la, A, m0, kb, lane, lw);
-    g7_lane_init<BKC>(lb, B, n0, kb, lane, lw);
-    auto issue = [&](int step, int stage) {   // steps are issued in order 0, 1, 2, ...
-      char* sa = smem + stage * G7_STAGE;
-      const int k0 = kb + 64 * step;
-      const bool tl = tail && step == nkt - 1;
-      g7_issue<AK>(A, la, sa, k0, ke, lane, lw, tl, cfast_a);
-      g7_issue<BKC>(B, lb, sa + G7_A, k0, ke, lane, lw, tl, cfast_b);
-    };
-    issue(0, 0);
-    if (nkt > 1) { issue(1, 1); asm volatile("s_waitcnt vmcnt(12)" ::: "memory"); }
-    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    int st = 2;
-    for (int t = 0; t < nkt; ++t) {
-      if (t + 2 < nkt) {
-        issue(t + 2, st);
-        st = st == 2 ? 0 : st + 1;
-      } else if (px) {
-        // rows 0..191 once the stage of step nkt - 3 is free, rows 192..255 a step later
-        if (t == nkt - 2 || nkt == 1) g7_issue_x(P, xs, ldx, smem, nkt, m0, n0, 0, 12, lane, lw);
-        if (t == nkt - 1) g7_issue_x(P, xs, ldx, smem, nkt, m0, n0, 192, 4, lane, lw);
-      }
-      if (t + 2 < nkt || (px && t == nkt - 2))
-        asm volatile("s_waitcnt vmcnt(12)" ::: "memory");   // step t+1 landed; t+2 (or the staged rows) in flight
-      else if (!px)
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      __builtin_amdgcn_s_barrier();
-    }
-    }
-    if (px) {   // the staged tile has landed
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      __builtin_amdgcn_s_barrier();
-    }
-    if (!P.lds_epi) return;
-    __syncthreads();   // the MFMA waves' C image is in LDS
-    g7_store_c<SM>(P, smem, m0, n0, nkt);
-    return;
-  }
-
-  // ------------------------------------------------------------------ MFMA waves
-  const int wm = wave >> 1, wn = wave & 1;
-  const bool do_ks = !AK && E.ksum && (tile % ntn) == 0 && wn == 0;
-  // forward layout: this lane's two 8-column bias chunks, loaded before the K loop (the
-  // MFMA waves issue no other global loads, so they land meanwhile) instead of one
-  // dependent round trip in the epilogue
-  const int ql = lane >> 4;
-  const bool pre_b = AK && BKC && !ws && E.bias && E.vec;
-  f32x4 pbias[2][2];
-#pragma unroll
-  for (int pr = 0; pr < 2; ++pr) {
-    const int n = n0 + wn * 64 + 16 * (2 * pr + (ql & 1)) + 8 * (ql >> 1);
-    pbias[pr][0] = pbias[pr][1] = f32x4{0.f, 0.f, 0.f, 0.f};
-    if (pre_b && n + 8 <= N) {
-      pbias[pr][0] = *reinterpret_cast<const f32x4*>(E.bias + n);
-      pbias[pr][1] = *reinterpret_cast<const f32x4*>(E.bias + n + 4);
-    }
-  }
-  // k-sums on the matrix core: an all-ones B fragment makes D[n][m] = sum_k A[m][k] (one
-  // extra MFMA per A fragment; summing the fragments on the VALU stalled the K loop)
-  f32x4 ksa[4];
-  Frag8<bf16> fones;
-#pragma unroll
-  for (int e = 0; e < 8; ++e) fones.v[e] = (bf16)1.f;
-#pragma unroll
-  for (int i = 0; i < 4; ++i) ksa[i] = f32x4{0.f, 0.f, 0.f, 0.f};
-  f32x4 acc[4][4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-  const uint32_t seed = (!ws && E.drop.thr) ? *E.drop.seed : 0u;
-  const bool px = P.pre_x && n0 + 128 <= N;
-  // the straight-line image epilogue's option set (wave-uniform), -1: the general path
-  const int fast = (P.lds_epi && m0 + 256 <= M && n0 + 128 <= N && (P.pre_x == 0 || px)) ? P.epi_fast : -1;
-  const bool pre_drop = fast >= 4 && fast <= 7;   // its dropout keep bits are hashed in the K loop
-  const int gps = (8 + nkt - 1) / nkt;            // keep-bit groups per K step
-  uint64_t dbits = 0;
-#if G7_PRIO
-  // waves w and w + 4 share a SIMD and run the same K loop in lockstep: the younger half at
-  // static priority 1 wins the VALU / issue arbitration it otherwise always loses
-  // (MI355X_MICROARCH.md, two waves per SIMD, item 4)
-  if (wave >= 4) __builtin_amdgcn_s_setprio(1);
-#endif
-  __builtin_amdgcn_s_barrier();
-  int stage = 0;
-  for (int t = 0; t < nkt; ++t) {
-    G7_STAMP(t, 0)
-    const char* sa = smem + stage * G7_STAGE;
-    const char* sb = sa + G7_A;
-#pragma unroll
-    for (int kk = 0; kk < 2; ++kk) {
-      Frag8<bf16> fa[4], fb[4];
-#pragma unroll
-      for (int i = 0; i < 4; ++i) g7_frag<AK>(fa[i], sa, wm * 64 + 16 * i, kk, lane);
-#pragma unroll
-      for (int j = 0; j < 4; ++j) g7_frag<BKC>(fb[j], sb, wn * 64 + 16 * j, kk, lane);
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) mma16(fb[j], fa[i], acc[i][j]);   // D[n][m]
-      if (!AK && do_ks) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) mma16(fones, fa[i], ksa[i]);
-      }
-    }
-    if (pre_drop) {   // VALU work beside this step's MFMAs
-      const int g1 = min(8, (t + 1) * gps);
-      for (int gi = t * gps; gi < g1; ++gi) {
-        const int m = m0 + wm * 64 + 16 * (gi >> 1) + (lane & 15);
-        const int n = n0 + wn * 64 + 16 * (2 * (gi & 1) + (ql & 1)) + 8 * (ql >> 1);
-        const uint32_t kb = drop_bits8(seed, E.drop.site, (uint32_t)((int64_t)m * E.n_log + n), E.drop.thr);
-        dbits |= (uint64_t)kb << (8 * gi);
-      }
-    }
-    stage = stage == 2 ? 0 : stage + 1;
-    G7_STAMP(t, 1)
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // this stage's reads retired (WAR vs the next copy)
-    __builtin_amdgcn_s_barrier();
-  }
-  G7_STAMP(nkt, 0)
-
-  if (!AK && do_ks) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const float ks = ksa[i][0];   // every lane of the row's column (lane & 15) holds it
-      const int m = m0 + wm * 64 + 16 * i + lane;
-      if (lane < 16 && m < M) {
-        if (ws) ws[(int64_t)P.splits * M * N + (int64_t)split * M + m] = ks;
-        else E.ksum[m] = E.ksum_beta != 0.f ? E.ksum_beta * E.ksum[m] + ks : ks;
-      }
-    }
-  }
-
-  // lane (q = lane >> 4) holds C[m][n0 + wn*64 + 16 j + 4 q + r] in acc[i][j][r]; swapping
-  // column blocks (2p, 2p+1) between row pairs q, q^1 leaves 8 consecutive columns per lane
-  const int q = ql;
-  if (px) __builtin_amdgcn_s_barrier();   // the loaders' staged residual / gate tile has landed
-  if (P.lds_epi) {
-    // epilogue values -> bf16 C image [256 rows][16 chunks of 16 B] (chunk c of row r at
-    // c ^ (r & 15): the 16 rows of one store instruction hit 16 different bank groups),
-    // then all 12 waves store whole 256-B row segments
-    switch (fast) {   // wave-uniform
-#define TT2_G7F(code, B_, R_, D_, X_)                                                                       \
-  case code:                                                                                                \
-    if constexpr (!B_ || (AK && BKC)) g7_epi_fast<B_, R_, D_, X_>(E, acc, pbias, smem, nkt, m0, n0, wm, wn, lane, dbits); \
-    break;
-      TT2_G7F(0, false, false, false, 0)
-      TT2_G7F(1, true, false, false, 0)
-      TT2_G7F(2, false, true, false, 0)
-      TT2_G7F(3, true, true, false, 0)
-      TT2_G7F(4, false, false, true, 0)
-      TT2_G7F(5, true, false, true, 0)
-      TT2_G7F(6, false, true, true, 0)
-      TT2_G7F(7, true, true, true, 0)
-      TT2_G7F(8, false, false, false, 1)
-      TT2_G7F(9, false, false, false, 2)
-#undef TT2_G7F
-      default:
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int r = wm * 64 + 16 * i + (lane & 15), m = m0 + r;
-#pragma unroll
-      for (int pr = 0; pr < 2; ++pr) {
-        float v[8];
-#pragma unroll
-        for (int rr = 0; rr < 4; ++rr) {
-          const auto sw = __builtin_amdgcn_permlane16_swap(__float_as_uint(acc[i][2 * pr][rr]),
-                                                           __float_as_uint(acc[i][2 * pr + 1][rr]), false, false);
-          v[rr] = __uint_as_float(sw[0]);
-          v[4 + rr] = __uint_as_float(sw[1]);
-        }
-        const int cl = wn * 64 + 16 * (2 * pr + (q & 1)) + 8 * (q >> 1), n = n0 + cl;
-        if (m >= M || n >= N) continue;
-        if (pre_b) {
-          const f32x4 b0 = pbias[pr][0], b1 = pbias[pr][1];
-#pragma unroll
-          for (int j = 0; j < 4; ++j) {
-            v[j] = v[j] * E.alpha + b0[j];
-            v[4 + j] = v[4 + j] * E.alpha + b1[j];
-          }
-        }
-        float o[8];
-        char* cp = smem + g7_img_row(nkt, r) + (((cl >> 3) ^ (r & 15)) << 4);   // C overwrites the staged chunk
-        epi_calc8(E, seed, m, n, v, pre_b, o, px && P.pre_x == 1 ? cp : nullptr, px && P.pre_x == 2 ? cp : nullptr);
-        bf16x8 x;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) x[j] = (bf16)o[j];
-        *reinterpret_cast<bf16x8*>(cp) = x;
-      }
-    }
-    }
-    G7_STAMP(nkt, 1)
-    __syncthreads();
-    G7_STAMP(nkt, 2)
-    g7_store_c<SM>(P, smem, m0, n0, nkt);
-    G7_STAMP(nkt, 3)
-    return;
-  }
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int m = m0 + wm * 64 + 16 * i + (lane & 15);
-#pragma unroll
-    for (int pr = 0; pr < 2; ++pr) {
-      float v[8];
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const auto sw = __builtin_amdgcn_permlane16_swap(__float_as_uint(acc[i][2 * pr][r]),
-                                                         __float_as_uint(acc[i][2 * pr + 1][r]), false, false);
-        v[r] = __uint_as_float(sw[0]);
-        v[4 + r] = __uint_as_float(sw[1]);
-      }
-      const int n = n0 + wn * 64 + 16 * (2 * pr + (q & 1)) + 8 * (q >> 1);
-      if (m >= M || n >= N) continue;
-      if (ws) {
-        float* w = ws + ((int64_t)split * M + m) * N + n;
-        if (n + 8 <= N && (N % 4) == 0) {
-          *reinterpret_cast<f32x4*>(w) = f32x4{v[0], v[1], v[2], v[3]};
-          *reinterpret_cast<f32x4*>(w + 4) = f32x4{v[4], v[5], v[6], v[7]};
-        } else {
-          for (int j = 0; j < 8; ++j)
-            if (n + j < N) w[j] = v[j];
-        }
-      } else if (pre_b && n + 8 <= N) {
-        const f32x4 b0 = pbias[pr][0], b1 = pbias[pr][1];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          v[j] = v[j] * E.alpha + b0[j];
-          v[4 + j] = v[4 + j] * E.alpha + b1[j];
-        }
-        epi_store8(E, seed, m, n, N, v, true);
-      } else {
-        epi_store8(E, seed, m, n, N, v);
-      }
-    }
-  }
-  G7_STAMP(nkt, 3)
-}
-
-// flat block index -> XCD-contiguous work item (blocks b and b + 8 share an XCD)
-TT2_DEV int xcd_item(int bid, int n) {
-  const int q = n / 8, r = n % 8, x = bid % 8;
-  return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + bid / 8;
-}
-
-template <bool AK, bool BKC, int SM = 0>
-__global__ __launch_bounds__(G7_NT, 1) void gemm7_kernel(G7Prob P) {
-  __shared__ __attribute__((aligned(1024))) char smem[G7_SMEM];
-  __shared__ int span_done;
-  G7_RT(0)
-  span_begin(P.span, &span_done);
-  const int u = xcd_item(blockIdx.x, P.items);
-  g7_item<AK, BKC, SM>(P, u % (P.items / P.splits), u / (P.items / P.splits), smem, P.span);
-  span_end(P.span, &span_done, G7_NT / 64);
-  G7_RT(1)
-}
-
-// Grouped launch: up to G7_MAXP independent problems of one layout (e.g. all weight
-// gradients of a layer, which share K = tokens), one workgroup per work item; items
-// G.ibase + blockIdx.x (tt2_gemm_grouped_ex launches a capped grid as several launches of
-// consecutive items, G.ibase a multiple of 8, so block b still runs on XCD b % 8).
-template <bool AK, bool BKC>
-__global__ __launch_bounds__(G7_NT, 1) void gemm7g_kernel(G7Group G) {
-  __shared__ __attribute__((aligned(1024))) char smem[G7_SMEM];
-  __shared__ int span_done;
-  span_begin(G.p[0].span, &span_done);
-  const int u = xcd_item(G.ibase + blockIdx.x, G.items);
-  int p = 0;
-#pragma unroll
-  for (int i = 1; i < G7_MAXP; ++i)
-    if (i < G.np && u >= G.p[i].item0) p = i;
-  const G7Prob& P = G.p[p];
-  const int local = u - P.item0, nt = P.items / P.splits;
-  g7_item<AK, BKC>(P, local % nt, local / nt, smem, G.p[0].span);
-  span_end(G.p[0].span, &span_done, G7_NT / 64);
-}
-
-// split-K reduce of every split problem of a group (blockIdx.y = problem); plane y = np, when
-// present, finalizes the deferred LayerNorm column sums (4 loads in flight per lane)
-__global__ void gemm_splitk_reduce_g(G7Group G) {
-  if (G.fin_only || (int)blockIdx.y == G.np) {
-    const G7Fin& f = G.fin;
-    const int o = blockIdx.x * G7_FIN_WAVES + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-    if (o >= 3 * f.C) return;
-    const int which = o / f.C, c = o - which * f.C;
-    float* dst = f.dst[which];
-    if (!dst) return;
-    const float* src = f.part + (int64_t)which * f.C + c;
-    const int64_t rs = 3 * (int64_t)f.C;
-    float acc[4] = {0.f, 0.f, 0.f, 0.f};
-    int r = lane;
-    for (; r + 192 < f.nb; r += 256) {
-#pragma unroll
-      for (int u = 0; u < 4; ++u) acc[u] += src[(r + 64 * u) * rs];
-    }
-    for (; r < f.nb; r += 64) acc[0] += src[r * rs];
-    const float v = wave_sum((acc[0] + acc[1]) + (acc[2] + acc[3]));
-    if (lane == 0) dst[c] = f.gb != 0.f ? f.gb * dst[c] + v : v;
-    return;
-  }
-  const G7Prob& P = G.p[blockIdx.y];
-  if (P.splits > 1) splitk_reduce_body(P.ws, P.splits, P.E, P.M, P.N, blockIdx.x, gridDim.x);
-}
-
-G7Prob g7_prob(const OpDesc& A, const OpDesc& B, const EpiParams& E, int M, int N, int K, int splits,
-                            float* ws) {
-  G7Prob P{A, B, E, M, N, K, K, 1, (N + 127) / 128, 0, 0, ws, 0, 0, -1, nullptr};
-  if (splits > 1) {
-    P.k_split = ((K + splits - 1) / splits + 63) / 64 * 64;
-    P.splits = (K + P.k_split - 1) / P.k_split;
-  }
-  P.items = ((M + 255) / 256) * P.ntn * P.splits;
-  return P;
-}
-
-// g7_epi_fast's option code for this launch, or -1 (general path): bias (forward layout, where
-// it is prefetched), ReLU, dropout, or one staged bf16 residual / gate alone; no beta.
-int g7_fast_code(const G7Prob& P, bool fwd) {
-  const EpiParams& E = P.E;
-  if (!P.lds_epi || E.beta != 0.f || E.act == ACT_TANH) return -1;
-  if (P.pre_x) {
-    const bool alone = !E.bias && E.act == ACT_NONE && !E.drop.thr && (P.pre_x == 1 ? !E.gate : !E.res);
-    return alone ? 7 + P.pre_x : -1;
-  }
-  if (E.res || E.gate) return -1;
-  if (E.bias && !fwd) return -1;
-  return (E.bias ? 1 : 0) | (E.act == ACT_RELU ? 2 : 0) | (E.drop.thr ? 4 : 0);
-}
-
-template <bool AK, bool BKC>
-hipError_t launch7(const OpDesc& A, const OpDesc& B, const EpiParams& E, int M, int N, int K, int splits, float* ws,
-                   hipStream_t s, bool lds_epi) {
-  G7Prob P = g7_prob(A, B, E, M, N, K, splits, ws);
-  P.lds_epi = lds_epi && P.splits == 1 && E.c_dt == TT2_BF16 && E.vec && (N % 8) == 0;
-  // the loader waves stage a bf16 residual / gate tile in LDS during the last K steps
-  P.pre_x = !P.lds_epi ? 0 : (E.res && E.res_dt == TT2_BF16) ? 1 : (E.gate && E.gate_dt == TT2_BF16) ? 2 : 0;
-  P.epi_fast = g7_fast_code(P, AK && BKC);
-  ProbeScope ps(s, P.items);
-  P.span = ps.span;
-  // fused BatchNorm statistics: own instantiations (the forward / dgrad conv layout only)
-  const int sm = E.cstats ? 1 : E.bnb.part ? 2 : 0;
-  auto go = [&](auto kern) {
-    if (ps.ext()) hipExtLaunchKernelGGL(kern, dim3(P.items), dim3(G7_NT), 0, s, ps.e0, ps.e1, 0, P);
-    else hipLaunchKernelGGL(kern, dim3(P.items), dim3(G7_NT), 0, s, P);
-  };
-  if constexpr (AK && BKC) {
-    if (sm == 1) go(gemm7_kernel<AK, BKC, 1>);
-    else if (sm == 2) go(gemm7_kernel<AK, BKC, 2>);
-    else go(gemm7_kernel<AK, BKC, 0>);
-  } else {
-    go(gemm7_kernel<AK, BKC, 0>);
-  }
-  if (P.splits > 1 && !E.main_only)
-    hipLaunchKernelGGL(gemm_splitk_reduce, dim3(splitk_blocks(M, N, E)), dim3(256), 0, s, ws, P.splits, E, M, N);
-  return hipGetLastError();
-}
-
-// =====================================================================================
-// v8 (bf16, A K-contiguous): 64 x 64 tiles for products whose 256 x 128 tiles cannot
-// fill the chip -- the encoder's 2048-row GEMMs give v7 32-96 tiles for 256 CUs, and a
-// lone v7 tile costs ~20k cycles however few CUs are busy.  512 threads: 4 MFMA waves,
-// each one 32 x 32 block on v_mfma_f32_32x32x16_bf16 (a single f32x16 accumulator), and
-// 4 loader waves that only issue LDS-DMA copies (as in v7: a wave that both copies into
-// LDS and reads it gets a compiler-inserted vmcnt(0) before its reads, which would drain
-// the pipeline every step).  Both operand tiles (64 rows x 64 k, 8 KB each) land in a
-// 4-stage ring three K steps ahead, one s_barrier per step; 64 KB of LDS per workgroup,
-// so two share a CU.  Images are 128-B rows with
-// chunk c of row r at slot c ^ g8_swz(r) (the attention tiles' swizzle): K-contiguous
-// operands are read as row fragments (two ds_read_b64), an N-contiguous B (dgrad) by
-// ds_read_b64_tr_b16; both deliver the same permuted k order, which the MFMA sums over.
-// Operands are swapped (D = B A^T) so each lane ends with one C row; a permlane32 swap
-// gives it 8 consecutive columns, the fused epilogue runs in registers, and the tile
-// leaves through LDS as whole 128-B rows.
-// =====================================================================================
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-#ifndef G8_RING   // ring stages (a power of two); the loaders run G8_RING - 1 steps ahead
-#define G8_RING 4
-#endif
-#ifndef G8_LOADERS   // loader waves: 4 (2 copies per operand per wave and step) or 8 (1).  8: the
-#define G8_LOADERS 8  // LDS-DMA issue rate, not the bytes in flight, bounded the K step
-#endif
-#ifndef G8_SPB   // K steps per barrier (64 deep each): 2 or 4 make the barrier cadence 128 / 256 deep
-#define G8_SPB 1
-#endif
-static_assert(G8_RING > G8_SPB && G8_RING % G8_SPB == 0, "v8 ring: whole barrier groups, one ahead at least");
-constexpr int G8_LW = G8_LOADERS, G8_PC = 8 / G8_LW;   // copies per operand tile per loader wave
-constexpr int G8_NT = 64 * (4 + G8_LW), G8_STAGES = G8_RING;   // 4 MFMA waves + the loader waves
-constexpr int G8_EPI = 512;   // threads of the C image store / fused statistics (64 rows x 8 chunks)
-constexpr int G8_TILE = 64 * 128;          // bytes per operand tile: 64 rows x 64 bf16
-constexpr int G8_STAGE = 2 * G8_TILE;
-
-TT2_DEV int g8_swz(int r) {
-  const int x = (r >> 1) & 7;
-  return ((x & 1) << 2) | (x >> 1);
-}
-
-// this wave's G8_PC of the 8 LDS-DMA copies of one operand tile (8 rows x 128 B each);
-// KC: tile rows are m / n and chunks run along k; MC: tile rows are k, chunks along n
-template <bool KC>
-TT2_DEV void g8_issue(const OpDesc& d, char* img, int r0, int k0, int lane, int wave) {
-#pragma unroll
-  for (int i = 0; i < G8_PC; ++i) {
-    const int inst = wave * G8_PC + i;
-    const int row = inst * 8 + (lane >> 3);
-    const int c = (lane & 7) ^ g8_swz(row);
-    const void* src = KC ? chunk_src(d, r0 + row, k0 + c * 8) : chunk_src(d, k0 + row, r0 + c * 8);
-    __builtin_amdgcn_global_load_lds((gvoid_t*)src, (lvoid_t*)(img + inst * 1024), 16, 0, 0);
-  }
-}
-
-// K-contiguous conv operand with C % 64 == 0 and K % 64 == 0 (as g7_conv_fast): each copy's
-// row offset and valid-tap mask are set once per tile; a step reads tap k0 / C.
-struct G8Conv { int64_t off[G8_PC]; uint32_t vm[G8_PC]; };
-TT2_DEV void g8_conv_init(const OpDesc& d, G8Conv& c, int r0, int lane, int wave) {
-#pragma unroll
-  for (int i = 0; i < G8_PC; ++i) {
-    const int row = (wave * G8_PC + i) * 8 + (lane >> 3), outer = r0 + row;
-    const int t = outer % d.conv_t;
-    const int lo = max(0, d.conv_pad - t), hi = min(31, d.conv_t - 1 - t + d.conv_pad);
-    c.off[i] = (int64_t)outer * d.ld + ((lane & 7) ^ g8_swz(row)) * 8 - (int64_t)d.conv_pad * d.conv_c;
-    c.vm[i] = outer < d.outer_max && hi >= lo ? (0xFFFFFFFFu >> (31 - hi)) & (0xFFFFFFFFu << lo) : 0u;
-  }
-}
-TT2_DEV void g8_issue_conv(const OpDesc& d, const G8Conv& c, char* img, int k0, int wave) {
-  const int tap = k0 / d.conv_c;
-  const bf16* p = reinterpret_cast<const bf16*>(d.p) + k0;
-#pragma unroll
-  for (int i = 0; i < G8_PC; ++i) {
-    const void* src = (c.vm[i] >> tap) & 1u ? (const void*)(p + c.off[i]) : (const void*)g_zero_page;
-    __builtin_amdgcn_global_load_lds((gvoid_t*)src, (lvoid_t*)(img + (wave * G8_PC + i) * 1024), 16, 0, 0);
-  }
-}
-
-// K-contiguous fragment of row `row`, k slice s (16 k): element j holds
-// k = 16 s + 8 (j >> 2) + 4 hi + (j & 3), the order the transposed read delivers
-TT2_DEV bf16x8 g8_frag_kc(const char* img, int row, int s, int hi) {
-  const char* r = img + row * 128 + 8 * hi;
-  const uint2 lo = *reinterpret_cast<const uint2*>(r + (((2 * s) ^ g8_swz(row)) << 4));
-  const uint2 up = *reinterpret_cast<const uint2*>(r + (((2 * s + 1) ^ g8_swz(row)) << 4));
-  union { uint4 u; bf16x8 v; } x;
-  x.u = make_uint4(lo.x, lo.y, up.x, up.y);
-  return x.v;
-}
-
-// N-contiguous fragment (image rows = k): column col0 + (lane & 31), same k order
-TT2_DEV bf16x8 g8_frag_mc(const char* img, int col0, int s, int lane) {
-  typedef __attribute__((address_space(3))) short4v lds_s4;
-  const int hi = lane >> 5, q = (lane >> 2) & 3, p = lane & 3, g = (lane >> 4) & 1;
-  const int col = col0 + 16 * g + 4 * p;
-  const int r0 = 16 * s + 4 * hi + q;
-  auto at = [&](int r) { return img + r * 128 + ((((col >> 3) ^ g8_swz(r))) << 4) + (col & 7) * 2; };
-  short4v lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4*)at(r0));
-  short4v up = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4*)at(r0 + 8));
-  union { short4v s[2]; bf16x8 v; } u;
-  u.s[0] = lo;
-  u.s[1] = up;
-  return u.v;
-}
-
-// v8's fused BatchNorm statistics (SM 1: col_stats moments, 2: bn_bwd sums; see g7_store_c): each
-// thread holds one row x 8 columns of the 64 x 64 image; the 8 rows of a wave that share a chunk
-// combine by shuffles, the 8 waves through a free ring slot, and 64 threads write the 64-row
-// chunk's value per column.
-template <int SM>
-TT2_DEV void g8_stats(const EpiParams& E, char* smem, int m0, int n0, int M, int N) {
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  const int rr = (tid >> 3) & 63, c = tid & 7, m = m0 + rr, n = n0 + 8 * c;
-  const bool ok = tid < G8_EPI && m < M && n < N;   // (8 loader waves: threads past 512 add nothing)
-  float v[8], s1[8], s2[8];
-  bf16x8_unpack(*reinterpret_cast<const u32x4*>(smem + rr * 128 + ((c ^ g8_swz(rr)) << 4)), v);
-  if constexpr (SM == 1) {
-    float k[8];
-    bf16x8_unpack(*reinterpret_cast<const u32x4*>(smem + ((c ^ g8_swz(0)) << 4)), k);
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const float d = ok ? v[j] - k[j] : 0.f;
-      s1[j] = d;
-      s2[j] = d * d;
-    }
-  } else {
-    const int mc = min(m, M - 1), nc = min(n, N - 8);
-    float yf[8];
-    bf16x8_unpack(*reinterpret_cast<const u32x4*>(E.bnb.y + (int64_t)mc * N + nc), yf);
-    const DropDesc& dd = E.bnb.drop;
-    const uint32_t seed = dd.thr ? *dd.seed : 0u;
-    const uint32_t bits = dd.thr ? drop_bits8(seed, dd.site, (uint32_t)((int64_t)m * N + n), dd.thr) : 0xFFu;
-    const float sc = dd.thr ? dd.scale : 1.f;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const float keep = (bits >> j) & 1u ? sc : 0.f;
-      const float xh = (yf[j] - E.bnb.mean[nc + j]) * E.bnb.rstd[nc + j];
-      const float z = act_f(E.bnb.act, xh * E.bnb.gamma[nc + j] + E.bnb.beta[nc + j]);
-      const float dp = ok ? v[j] * keep * act_grad_from_out(E.bnb.act, z) : 0.f;
-      s1[j] = dp;
-      s2[j] = dp * xh;
-    }
-  }
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {   // lanes c, c + 8, ..., c + 56: the wave's 8 rows of this chunk
-    s1[j] += __shfl_xor(s1[j], 8);
-    s2[j] += __shfl_xor(s2[j], 8);
-    s1[j] += __shfl_xor(s1[j], 16);
-    s2[j] += __shfl_xor(s2[j], 16);
-    s1[j] += __shfl_xor(s1[j], 32);
-    s2[j] += __shfl_xor(s2[j], 32);
-  }
-  float* red = reinterpret_cast<float*>(smem + 2 * G8_STAGE);   // [8 waves][64 cols][2], past the image
-  if (lane < 8 && w < G8_EPI / 64) {
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      red[(w * 64 + 8 * c + j) * 2 + 0] = s1[j];
-      red[(w * 64 + 8 * c + j) * 2 + 1] = s2[j];
-    }
-  }
-  __syncthreads();
-  if (tid < 64 && n0 + tid < N) {
-    float S1 = 0.f, S2 = 0.f;
-    for (int q = 0; q < G8_EPI / 64; ++q) {
-      S1 += red[(q * 64 + tid) * 2 + 0];
-      S2 += red[(q * 64 + tid) * 2 + 1];
-    }
-    float* out = (SM == 1 ? E.cstats : E.bnb.part) + (int64_t)(m0 / 64) * 2 * N + n0 + tid;
-    if constexpr (SM == 1) {
-      const int cc = tid >> 3;
-      const float kt = __uint_as_float((uint32_t)*reinterpret_cast<const uint16_t*>(
-                                           smem + ((cc ^ g8_swz(0)) << 4) + 2 * (tid & 7)) << 16);
-      const float nr = (float)min(64, M - m0);
-      out[0] = kt + S1 / nr;
-      out[N] = fmaxf(S2 - S1 * S1 / nr, 0.f);
-    } else {
-      out[0] = S1;
-      out[N] = S2;
-    }
-  }
-}
-
-template <bool BKC, int SM = 0>
-__global__ __launch_bounds__(G8_NT, G8_STAGES <= 4 ? 2 : 1) void gemm8_kernel(OpDesc A, OpDesc B, EpiParams E, int M, int N, int K,
-                                                         int ntn, int items, unsigned long long* span) {
-  __shared__ __attribute__((aligned(1024))) char smem[G8_STAGES * G8_STAGE];
-  __shared__ int span_done;
-  span_begin(span, &span_done);
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, hi = lane >> 5;
-  const int tile = xcd_item(blockIdx.x, items);
-  const int m0 = (tile / ntn) * 64, n0 = (tile % ntn) * 64;
-  const int nkt = (K + 63) / 64;
-  if (wave >= 4) {   // ---------------------------------------------- loader waves
-    const int lw = wave - 4;
-    const bool afast = A.conv_t > 0 && (A.conv_c & 63) == 0 && (K & 63) == 0;
-    G8Conv ca;
-    if (afast) g8_conv_init(A, ca, m0, lane, lw);
-    auto issue = [&](int t) {
-      char* st = smem + (t & (G8_STAGES - 1)) * G8_STAGE;
-      if (afast) g8_issue_conv(A, ca, st, 64 * t, lw);
-      else g8_issue<true>(A, st, m0, 64 * t, lane, lw);
-      g8_issue<BKC>(B, st + G8_TILE, n0, 64 * t, lane, lw);
-    };
-    // G8_STAGES - G8_SPB steps ahead; each step is 2 G8_PC copies per loader wave
-    constexpr int AH = G8_STAGES - G8_SPB;
-    auto wait_ahead = [](int ahead) {   // step t+1 landed, `ahead` later steps may stay in flight
-      switch (ahead * 2 * G8_PC) {        // copies per step and wave: 2 G8_PC
-        case 24: asm volatile("s_waitcnt vmcnt(24)" ::: "memory"); break;
-        case 20: asm volatile("s_waitcnt vmcnt(20)" ::: "memory"); break;
-        case 16: asm volatile("s_waitcnt vmcnt(16)" ::: "memory"); break;
-        case 14: asm volatile("s_waitcnt vmcnt(14)" ::: "memory"); break;
-        case 12: asm volatile("s_waitcnt vmcnt(12)" ::: "memory"); break;
-        case 10: asm volatile("s_waitcnt vmcnt(10)" ::: "memory"); break;
-        case 8: asm volatile("s_waitcnt vmcnt(8)" ::: "memory"); break;
-        case 6: asm volatile("s_waitcnt vmcnt(6)" ::: "memory"); break;
-        case 4: asm volatile("s_waitcnt vmcnt(4)" ::: "memory"); break;
-        case 2: asm volatile("s_waitcnt vmcnt(2)" ::: "memory"); break;
-        default: asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      }
-    };
-    for (int t = 0; t < AH && t < nkt; ++t) issue(t);
-    wait_ahead(min(AH, nkt) - G8_SPB);   // steps 0 .. G8_SPB - 1 landed
-    __builtin_amdgcn_s_barrier();
-    for (int t = 0; t < nkt; t += G8_SPB) {
-#pragma unroll
-      for (int j = 0; j < G8_SPB; ++j)   // into the stages steps t - G8_SPB .. t - 1 used: free since the last barrier
-        if (t + AH + j < nkt) issue(t + AH + j);
-      wait_ahead(min(AH - G8_SPB, nkt - 2 * G8_SPB - t));
-      __builtin_amdgcn_s_barrier();    // steps t + G8_SPB .. t + 2 G8_SPB - 1 landed
-    }
-  } else {   // ------------------------------------------------------- MFMA waves
-    const int wm = wave >> 1, wn = wave & 1;
-    f32x16 acc;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) acc[i] = 0.f;
-    __builtin_amdgcn_s_barrier();
-    for (int t0 = 0; t0 < nkt; t0 += G8_SPB) {
-#pragma unroll
-      for (int j = 0; j < G8_SPB; ++j) {
-        const int t = t0 + j;
-        if (G8_SPB > 1 && t >= nkt) break;
-        const char* sa = smem + (t & (G8_STAGES - 1)) * G8_STAGE;
-        const char* sb = sa + G8_TILE;
-#pragma unroll
-        for (int s = 0; s < 4; ++s) {
-          const bf16x8 fa = g8_frag_kc(sa, wm * 32 + (lane & 31), s, hi);
-          const bf16x8 fb = BKC ? g8_frag_kc(sb, wn * 32 + (lane & 31), s, hi) : g8_frag_mc(sb, wn * 32, s, lane);
-          acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fb, fa, acc, 0, 0, 0);   // D[n][m]
-        }
-      }
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // these stages' reads retired before they are re-filled
-      __builtin_amdgcn_s_barrier();
-    }
-    // lane holds C[m0 + 32 wm + (lane & 31)][n0 + 32 wn + (r & 3) + 8 (r >> 2) + 4 hi]; the
-    // permlane32 swap of register groups (0,1) and (2,3) leaves 8 consecutive columns per lane.
-    // The ring is free (every wave passed the last barrier): it takes the C image [64][128 B].
-    const int r = wm * 32 + (lane & 31), m = m0 + r;
-    const uint32_t seed = E.drop.thr ? *E.drop.seed : 0u;
-#pragma unroll
-    for (int pr = 0; pr < 2; ++pr) {
-      float v[8];
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(acc[8 * pr + i]),
-                                                         __float_as_uint(acc[8 * pr + 4 + i]), false, false);
-        v[i] = __uint_as_float(sw[0]);
-        v[4 + i] = __uint_as_float(sw[1]);
-      }
-      const int cl = wn * 32 + 16 * pr + 8 * hi, n = n0 + cl;
-      if (m >= M || n >= N) continue;
-      float o[8];
-      epi_calc8(E, seed, m, n, v, false, o);
-      bf16x8 x;
-#pragma unroll
-      for (int j = 0; j < 8; ++j) x[j] = (bf16)o[j];
-      *reinterpret_cast<bf16x8*>(smem + r * 128 + (((cl >> 3) ^ g8_swz(r)) << 4)) = x;
-    }
-  }
-  __syncthreads();   // the C image is complete: 512 threads store whole 128-B rows
-  bf16* C = reinterpret_cast<bf16*>(E.c);
-  const int id = tid, rr = id >> 3, c = id & 7, mm = m0 + rr, nn = n0 + 8 * c;
-  if (tid < G8_EPI && mm < M && nn < N)   // nontemporal, as v7's C (g7_store_c)
-    __builtin_nontemporal_store(*reinterpret_cast<const u32x4*>(smem + rr * 128 + ((c ^ g8_swz(rr)) << 4)),
-                                reinterpret_cast<u32x4*>(C + (int64_t)mm * E.ldc + nn));
-  if constexpr (SM != 0) g8_stats<SM>(E, smem, m0, n0, M, N);
-  span_end(span, &span_done, G8_NT / 64);
-}
-
-template <bool BKC>
-hipError_t launch8(const OpDesc& A, const OpDesc& B, const EpiParams& E, int M, int N, int K, hipStream_t s) {
-  const int ntn = (N + 63) / 64, items = ((M + 63) / 64) * ntn;
-  ProbeScope ps(s, items);
-  auto go = [&](auto kern) {
-    if (ps.ext())
-      hipExtLaunchKernelGGL(kern, dim3(items), dim3(G8_NT), 0, s, ps.e0, ps.e1, 0, A, B, E, M, N, K, ntn, items,
-                            ps.span);
-    else
-      hipLaunchKernelGGL(kern, dim3(items), dim3(G8_NT), 0, s, A, B, E, M, N, K, ntn, items, ps.span);
-  };
-  if (E.cstats) go(gemm8_kernel<BKC, 1>);   // fused BatchNorm statistics (64-row chunks)
-  else if (E.bnb.part) go(gemm8_kernel<BKC, 2>);
-  else go(gemm8_kernel<BKC, 0>);
-  return hipGetLastError();
-}
-
-
-// =====================================================================================
-// v10 (bf16, NT: A and B K-contiguous): 256 x 256 tile for the wide forward products.  v7's
-// K loop is bound by how fast its loader waves fill LDS (48 KB per 256 x 128 x 64 step against
-// 1,024 MFMA cycles); a 256 x 256 tile stages 64 KB for twice the MFMA work.  768 threads as
-// v7: 8 MFMA waves (2 M x 4 N, 128 x 64 each: 128 accumulators per lane, the bias loaded after
-// the K loop to stay within 168 VGPRs) and 4 loader waves.  The ring is 5 slots of one
-// operand's 64-deep tile (32 KB: all 160 KB of LDS), filled in the order A_0 B_0 A_1 B_1 A_2
-// ...: after the barrier that ends step t - 1 its two slots take B_{t+1} and A_{t+2}, so the
-// activation operand (cold: just written by the previous kernel) is issued two steps ahead and
-// the weight operand (L2-resident) one step ahead.  Images, swizzles and fragment reads are
-// v7's; the epilogue is v7's straight-line form into an LDS C image of two 128-column halves.
-// =====================================================================================
-constexpr int G10_NT = 768;
-constexpr int G10_SLOT = 256 * 128;              // one operand's 64-deep tile: 256 rows x 128 B
-constexpr int G10_SLOTS = 5;
-constexpr int G10_SMEM = G10_SLOTS * G10_SLOT;   // 160 KB: the whole LDS
-
-TT2_DEV int g10_img(int r, int cl) {
-  return (cl >> 7) * 65536 + r * 256 + ((((cl >> 3) & 15) ^ (r & 15)) << 4);
-}
-
-TT2_DEV void g10_wait(int n) {   // s_waitcnt vmcnt(n), n a multiple of 8 (one item per loader wave)
-  if (n >= 24) asm volatile("s_waitcnt vmcnt(24)" ::: "memory");
-  else if (n >= 16) asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
-  else if (n >= 8) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-  else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-}
-
-template <int CODE>   // g7_fast_code: bit 0 bias, bit 1 ReLU, bit 2 dropout
-__global__ __launch_bounds__(G10_NT, 1) void gemm10_kernel(OpDesc A, OpDesc B, EpiParams E, int M, int N, int K,
-                                                           int ntn, int items, unsigned long long* span) {
-  constexpr bool BIAS = CODE & 1, RELU = CODE & 2, DROP = CODE & 4;
-  __shared__ __attribute__((aligned(1024))) char smem[G10_SMEM];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  if (span && tid == 0) span[TT2_SPAN_W * blockIdx.x] = wall_clock64();
-#ifdef TT2_PHASE
-  unsigned long long* srec = span ? span + TT2_SPAN_W * blockIdx.x : nullptr;
-  if (srec && tid == 0) srec[2] = __builtin_amdgcn_s_memtime();
-#endif
-  const int tile = xcd_item(blockIdx.x, items);
-  const int m0 = (tile / ntn) * 256, n0 = (tile % ntn) * 256;
-  const int nkt = K / 64, nit = 2 * nkt;   // ring items: A_t = 2 t, B_t = 2 t + 1
-  if (wave >= 8) {   // ------------------------------------------------ loader waves
-    const int lw = wave - 8;
-    G7Lane<8> la, lb;   // 8 of each operand tile's 32 copies
-    g7_lane_init<true>(la, A, m0, 0, lane, lw);
-    g7_lane_init<true>(lb, B, n0, 0, lane, lw);
-    auto issue = [&](int it) {
-      char* dst = smem + (it % G10_SLOTS) * G10_SLOT;
-      if (it & 1) g7_issue<true>(B, lb, dst, 64 * (it >> 1), K, lane, lw, false, false);
-      else g7_issue<true>(A, la, dst, 64 * (it >> 1), K, lane, lw, false, false);
-    };
-    const int pre = min(G10_SLOTS, nit);
-    for (int it = 0; it < pre; ++it) issue(it);
-    g10_wait(8 * (pre - 2));   // A_0, B_0 landed
-    __builtin_amdgcn_s_barrier();
-    for (int t = 0; t < nkt; ++t) {
-      if (t >= 1) {   // the slots step t - 1 read: B_{t+1}, A_{t+2}
-        if (2 * t + 3 < nit) issue(2 * t + 3);
-        if (2 * t + 4 < nit) issue(2 * t + 4);
-      }
-      if (t + 1 < nkt) {   // B_{t+1} landed: only A_{t+2}, issued after it, may stay in flight
-        const int last = min(nit - 1, max(G10_SLOTS - 1, 2 * t + 4));
-        g10_wait(8 * (last - (2 * t + 3)));
-      }
-      __builtin_amdgcn_s_barrier();
-    }
-  } else {   // ------------------------------------------------------- MFMA waves
-    const int wm = wave >> 2, wn = wave & 3, q = lane >> 4;
-    f32x4 acc[8][4];
-#pragma unroll
-    for (int i = 0; i < 8; ++i)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-    const uint32_t seed = DROP ? *E.drop.seed : 0u;
-    const int gps = (16 + nkt - 1) / nkt;   // keep-bit groups (16-row block i, column pair pr) per K step
-    uint64_t dbits[2] = {0, 0};
-#if G7_PRIO
-    if (wave >= 4) __builtin_amdgcn_s_setprio(1);   // as v7: the younger wave of each SIMD's pair
-#endif
-    __builtin_amdgcn_s_barrier();
-    for (int t = 0; t < nkt; ++t) {
-      G7_STAMP(t, 0)
-      const char* sa = smem + ((2 * t) % G10_SLOTS) * G10_SLOT;
-      const char* sb = smem + ((2 * t + 1) % G10_SLOTS) * G10_SLOT;
-#pragma unroll
-      for (int kk = 0; kk < 2; ++kk) {
-        Frag8<bf16> fb[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) g7_frag<true>(fb[j], sb, wn * 64 + 16 * j, kk, lane);
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-          Frag8<bf16> fa;
-          g7_frag<true>(fa, sa, wm * 128 + 16 * i, kk, lane);
-#pragma unroll
-          for (int j = 0; j < 4; ++j) mma16(fb[j], fa, acc[i][j]);   // D[n][m]
-        }
-      }
-      if (DROP) {   // VALU work beside this step's MFMAs
-        const int g1 = min(16, (t + 1) * gps);
-        for (int gi = t * gps; gi < g1; ++gi) {
-          const int m = m0 + wm * 128 + 16 * (gi >> 1) + (lane & 15);
-          const int n = n0 + wn * 64 + 16 * (2 * (gi & 1) + (q & 1)) + 8 * (q >> 1);
-          const uint64_t kb = drop_bits8(seed, E.drop.site, (uint32_t)((int64_t)m * E.n_log + n), E.drop.thr);
-          dbits[gi >> 3] |= kb << (8 * (gi & 7));
-        }
-      }
-      G7_STAMP(t, 1)
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // this step's reads retired (WAR vs its slots)
-      __builtin_amdgcn_s_barrier();
-    }
-    G7_STAMP(nkt, 0)
-    // epilogue: alpha, bias, ReLU, dropout (v7's order) into the C image (the ring is free)
-    f32x4 pbias[2][2];
-#pragma unroll
-    for (int pr = 0; pr < 2; ++pr) {
-      const int n = n0 + wn * 64 + 16 * (2 * pr + (q & 1)) + 8 * (q >> 1);
-      pbias[pr][0] = pbias[pr][1] = f32x4{0.f, 0.f, 0.f, 0.f};
-      if (BIAS) {
-        pbias[pr][0] = *reinterpret_cast<const f32x4*>(E.bias + n);
-        pbias[pr][1] = *reinterpret_cast<const f32x4*>(E.bias + n + 4);
-      }
-    }
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-      const int r = wm * 128 + 16 * i + (lane & 15);
-#pragma unroll
-      for (int pr = 0; pr < 2; ++pr) {
-        float v[8];
-#pragma unroll
-        for (int rr = 0; rr < 4; ++rr) {
-          const auto sw = __builtin_amdgcn_permlane16_swap(__float_as_uint(acc[i][2 * pr][rr]),
-                                                           __float_as_uint(acc[i][2 * pr + 1][rr]), false, false);
-          v[rr] = __uint_as_float(sw[0]);
-          v[4 + rr] = __uint_as_float(sw[1]);
-        }
-        const int cl = wn * 64 + 16 * (2 * pr + (q & 1)) + 8 * (q >> 1);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          v[j] = BIAS ? v[j] * E.alpha + pbias[pr][0][j] : v[j] * E.alpha;
-          v[4 + j] = BIAS ? v[4 + j] * E.alpha + pbias[pr][1][j] : v[4 + j] * E.alpha;
-        }
-        if (RELU) {
-#pragma unroll
-          for (int j = 0; j < 8; ++j) v[j] = fmaxf(v[j], 0.f);
-        }
-        if (DROP) {
-          const int gi = 2 * i + pr;
-          const uint32_t kb = (uint32_t)(dbits[gi >> 3] >> (8 * (gi & 7)));
-#pragma unroll
-          for (int j = 0; j < 8; ++j) v[j] = (kb >> j) & 1u ? v[j] * E.drop.scale : 0.f;
-        }
-        bf16x8 x;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) x[j] = (bf16)v[j];
-        *reinterpret_cast<bf16x8*>(smem + g10_img(r, cl)) = x;
-      }
-    }
-    G7_STAMP(nkt, 1)
-  }
-  __syncthreads();   // the C image is complete: all 12 waves store whole 256-B row segments
-  if (wave == 0) { G7_STAMP(nkt, 2) }
-  bf16* C = reinterpret_cast<bf16*>(E.c);
-  for (int id = tid; id < 256 * 32; id += G10_NT) {
-    const int half = id >> 12, r = (id >> 4) & 255, c = id & 15;
-    const int mm = m0 + r, nn = n0 + half * 128 + 8 * c;
-    if (mm < M)   // nontemporal, as v7's C
-      __builtin_nontemporal_store(*reinterpret_cast<const u32x4*>(smem + half * 65536 + r * 256 + ((c ^ (r & 15)) << 4)),
-                                  reinterpret_cast<u32x4*>(C + (int64_t)mm * E.ldc + nn));
-  }
-  if (wave == 0) { G7_STAMP(nkt, 3) }
-  if (span) {   // every wave's stores completed, then one end stamp
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-#ifdef TT2_PHASE
-    if (tid == 0) span[TT2_SPAN_W * blockIdx.x + 31] = __builtin_amdgcn_s_memtime();
-#endif
-    if (tid == 0) span[TT2_SPAN_W * blockIdx.x + 1] = wall_clock64();
-  }
-}
-
-hipError_t launch10(const OpDesc& A, const OpDesc& B, const EpiParams& E, int M, int N, int K, int code,
-                    hipStream_t s) {
-  const int ntn = N / 256, items = ((M + 255) / 256) * ntn;
-  ProbeScope ps(s, items);
-#define TT2_G10(C_)                                                                                               \
-  case C_:                                                                                                        \
-    if (ps.ext())                                                                                                 \
-      hipExtLaunchKernelGGL((gemm10_kernel<C_>), dim3(items), dim3(G10_NT), 0, s, ps.e0, ps.e1, 0, A, B, E, M, N, \
-                            K, ntn, items, ps.span);                                                              \
-    else                                                                                                          \
-      hipLaunchKernelGGL((gemm10_kernel<C_>), dim3(items), dim3(G10_NT), 0, s, A, B, E, M, N, K, ntn, items,       \
-                         ps.span);                                                                                \
-    break;
-  switch (code) {
-    TT2_G10(0) TT2_G10(1) TT2_G10(2) TT2_G10(3) TT2_G10(4) TT2_G10(5) TT2_G10(6) TT2_G10(7)
-    default: return hipErrorInvalidValue;
-  }
-#undef TT2_G10
-  return hipGetLastError();
-}
-
-// v10's epilogue code for this launch, or -1: bf16 C on 16-B rows, no beta / residual / gate /
-// tanh / k-sums (g7_fast_code's forward option sets)
-// =====================================================================================
-// v11: v7's 256 x 128 tile with v10's MFMA-wave layout and twice the loader waves.  The K loop
-// of v7 is bound by its 4 loader waves' LDS-DMA issue rate (12 copies per wave per step:
-// round 2's ablation, loads removed, and round 6's v8, whose K step fell 22 % with 8 loader
-// waves), and v7 cannot add loader waves: 8 MFMA waves at ~146 VGPRs leave room for 12 waves
-// per CU.  Here 4 MFMA waves (2 M x 2 N, 128 x 64 each: v10's 128 accumulators per lane, one
-// wave per SIMD) and 8 loader waves (6 copies each per 48 KB step: A 4, B 2) into v7's 3-stage
-// ring, with v7's images, swizzles and fragment reads.  The MFMA waves read 96 KB of fragments
-// per step instead of v7's 128 KB.  NT, plain bf16 operands, K % 64 == 0, N % 128 == 0, the
-// v10 epilogue codes (bias, ReLU, dropout); the C image goes where v7's does (g7_img_row).
-// =====================================================================================
-constexpr int G11_NT = 768;
-
-// CODE: bit 0 bias, bit 1 ReLU, bit 2 dropout (the forward's options, with BKC: NT); 8: a bf16
-// residual added, 16: a bf16 ReLU gate (the activation gradients, !BKC: B N-contiguous), whose
-// tile the loader waves stage into the C image during the last two K steps (v7's G7_X_AUX copies)
-template <bool BKC, int CODE>
-__global__ __launch_bounds__(G11_NT, 1) void gemm11_kernel(OpDesc A, OpDesc B, EpiParams E, int M, int N, int K,
-                                                           int ntn, int items, unsigned long long* span) {
-  constexpr bool BIAS = CODE & 1, RELU = CODE & 2, DROP = CODE & 4;
-  constexpr int PX = CODE & 8 ? 1 : CODE & 16 ? 2 : 0;   // staged epilogue operand: residual / gate
-  __shared__ __attribute__((aligned(1024))) char smem[G7_SMEM];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  if (span && tid == 0) span[TT2_SPAN_W * blockIdx.x] = wall_clock64();
-  const int tile = xcd_item(blockIdx.x, items);
-  const int m0 = (tile / ntn) * 256, n0 = (tile % ntn) * 128;
-  const int nkt = K / 64;
-  if (wave >= 4) {   // ------------------------------------------------ loader waves
-    const int lw = wave - 4;
-    G7Lane<4> la;   // 4 of the A tile's 32 copies, 2 of the B tile's 16
-    G7Lane<2> lb;
-    g7_lane_init<true>(la, A, m0, 0, lane, lw);
-    g7_lane_init<BKC>(lb, B, n0, 0, lane, lw);
-    auto issue = [&](int step, int stage) {
-      char* sa = smem + stage * G7_STAGE;
-      g7_issue<true>(A, la, sa, 64 * step, K, lane, lw, false, false);
-      g7_issue<BKC>(B, lb, sa + G7_A, 64 * step, K, lane, lw, false, false);
-    };
-    // the residual / gate tile (PX), 6 + 2 copies per wave into the image's rows 0..191 (the stage
-    // of step nkt - 3) and 192..255 (step nkt - 2), each once its stage is free
-    G7Prob px_p;
-    px_p.M = M;
-    const void* xs = PX == 1 ? E.res : E.gate;
-    const int64_t ldx = PX == 1 ? E.ldr : E.ldg;
-    issue(0, 0);
-    if (nkt > 1) { issue(1, 1); asm volatile("s_waitcnt vmcnt(6)" ::: "memory"); }
-    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    int st = 2;
-    for (int t = 0; t < nkt; ++t) {
-      if (t + 2 < nkt) {
-        issue(t + 2, st);
-        st = st == 2 ? 0 : st + 1;
-      } else if (PX) {
-        if (t == nkt - 2 || nkt == 1) g7_issue_x(px_p, xs, ldx, smem, nkt, m0, n0, 0, 6, lane, lw);
-        if (t == nkt - 1) g7_issue_x(px_p, xs, ldx, smem, nkt, m0, n0, 192, 2, lane, lw);
-      }
-      if (t + 2 < nkt || (PX && t == nkt - 2))
-        asm volatile("s_waitcnt vmcnt(6)" ::: "memory");   // step t+1 landed; t+2 (or the staged rows) in flight
-      else if (!PX)
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      __builtin_amdgcn_s_barrier();
-    }
-    if (PX) {   // the staged tile has landed
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      __builtin_amdgcn_s_barrier();
-    }
-  } else {   // ------------------------------------------------------- MFMA waves
-    const int wm = wave >> 1, wn = wave & 1, q = lane >> 4;
-    f32x4 acc[8][4];
-#pragma unroll
-    for (int i = 0; i < 8; ++i)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-    const uint32_t seed = DROP ? *E.drop.seed : 0u;
-    const int gps = (16 + nkt - 1) / nkt;   // keep-bit groups (16-row block i, column pair pr) per K step
-    uint64_t dbits[2] = {0, 0};
-    __builtin_amdgcn_s_barrier();
-    int stage = 0;
-    for (int t = 0; t < nkt; ++t) {
-      const char* sa = smem + stage * G7_STAGE;
-      const char* sb = sa + G7_A;
-#pragma unroll
-      for (int kk = 0; kk < 2; ++kk) {
-        Frag8<bf16> fb[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) g7_frag<BKC>(fb[j], sb, wn * 64 + 16 * j, kk, lane);
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-          Frag8<bf16> fa;
-          g7_frag<true>(fa, sa, wm * 128 + 16 * i, kk, lane);
-#pragma unroll
-          for (int j = 0; j < 4; ++j) mma16(fb[j], fa, acc[i][j]);   // D[n][m]
-        }
-      }
-      if (DROP) {   // VALU work beside this step's MFMAs
-        const int g1 = min(16, (t + 1) * gps);
-        for (int gi = t * gps; gi < g1; ++gi) {
-          const int m = m0 + wm * 128 + 16 * (gi >> 1) + (lane & 15);
-          const int n = n0 + wn * 64 + 16 * (2 * (gi & 1) + (q & 1)) + 8 * (q >> 1);
-          const uint64_t kb = drop_bits8(seed, E.drop.site, (uint32_t)((int64_t)m * E.n_log + n), E.drop.thr);
-          dbits[gi >> 3] |= kb << (8 * (gi & 7));
-        }
-      }
-      stage = stage == 2 ? 0 : stage + 1;
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // this stage's reads retired (WAR vs the next copy)
-      __builtin_amdgcn_s_barrier();
-    }
-    if (PX) __builtin_amdgcn_s_barrier();   // the loaders' staged residual / gate tile has landed
-    // epilogue: alpha, bias, residual, ReLU, gate, dropout (v7's order) into v7's C image
-    f32x4 pbias[2][2];
-#pragma unroll
-    for (int pr = 0; pr < 2; ++pr) {
-      const int n = n0 + wn * 64 + 16 * (2 * pr + (q & 1)) + 8 * (q >> 1);
-      pbias[pr][0] = pbias[pr][1] = f32x4{0.f, 0.f, 0.f, 0.f};
-      if (BIAS) {
-        pbias[pr][0] = *reinterpret_cast<const f32x4*>(E.bias + n);
-        pbias[pr][1] = *reinterpret_cast<const f32x4*>(E.bias + n + 4);
-      }
-    }
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-      const int r = wm * 128 + 16 * i + (lane & 15);
-#pragma unroll
-      for (int pr = 0; pr < 2; ++pr) {
-        float v[8];
-#pragma unroll
-        for (int rr = 0; rr < 4; ++rr) {
-          const auto sw = __builtin_amdgcn_permlane16_swap(__float_as_uint(acc[i][2 * pr][rr]),
-                                                           __float_as_uint(acc[i][2 * pr + 1][rr]), false, false);
-          v[rr] = __uint_as_float(sw[0]);
-          v[4 + rr] = __uint_as_float(sw[1]);
-        }
-        const int cl = wn * 64 + 16 * (2 * pr + (q & 1)) + 8 * (q >> 1);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          v[j] = BIAS ? v[j] * E.alpha + pbias[pr][0][j] : v[j] * E.alpha;
-          v[4 + j] = BIAS ? v[4 + j] * E.alpha + pbias[pr][1][j] : v[4 + j] * E.alpha;
-        }
-        char* cp = smem + g7_img_row(nkt, r) + (((cl >> 3) ^ (r & 15)) << 4);   // C overwrites the staged chunk
-        if (PX) {
-          float tx[8];
-          unpack_lds8(cp, tx);
-#pragma unroll
-          for (int j = 0; j < 8; ++j) {
-            if (PX == 1) v[j] += tx[j];
-            else v[j] = tx[j] != 0.f ? v[j] * E.gate_scale : 0.f;
-          }
-        }
-        if (RELU) {
-#pragma unroll
-          for (int j = 0; j < 8; ++j) v[j] = fmaxf(v[j], 0.f);
-        }
-        if (DROP) {
-          const int gi = 2 * i + pr;
-          const uint32_t kb = (uint32_t)(dbits[gi >> 3] >> (8 * (gi & 7)));
-#pragma unroll
-          for (int j = 0; j < 8; ++j) v[j] = (kb >> j) & 1u ? v[j] * E.drop.scale : 0.f;
-        }
-        bf16x8 x;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) x[j] = (bf16)v[j];
-        *reinterpret_cast<bf16x8*>(cp) = x;
-      }
-    }
-  }
-  __syncthreads();   // the C image is complete: all 12 waves store whole 256-B row segments
-  bf16* C = reinterpret_cast<bf16*>(E.c);
-  for (int id = tid; id < 256 * 16; id += G11_NT) {
-    const int r = id >> 4, c = id & 15;
-    const int mm = m0 + r, nn = n0 + 8 * c;
-    if (mm < M)   // nontemporal, as v7's C
-      __builtin_nontemporal_store(*reinterpret_cast<const u32x4*>(smem + g7_img_row(nkt, r) + ((c ^ (r & 15)) << 4)),
-                                  reinterpret_cast<u32x4*>(C + (int64_t)mm * E.ldc + nn));
-  }
-  if (span) {   // every wave's stores completed, then one end stamp
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (tid == 0) span[TT2_SPAN_W * blockIdx.x + 1] = wall_clock64();
-  }
-}
-
-hipError_t launch11(const OpDesc& A, const OpDesc& B, const EpiParams& E, int M, int N, int K, bool bkc, int code,
-                    hipStream_t s) {
-  const int ntn = N / 128, items = ((M + 255) / 256) * ntn;
-  ProbeScope ps(s, items);
-#define TT2_G11(BK_, C_)                                                                                          \
-  case C_:                                                                                                        \
-    if (ps.ext())                                                                                                 \
-      hipExtLaunchKernelGGL((gemm11_kernel<BK_, C_>), dim3(items), dim3(G11_NT), 0, s, ps.e0, ps.e1, 0, A, B, E, M, \
-                            N, K, ntn, items, ps.span);                                                           \
-    else                                                                                                          \
-      hipLaunchKernelGGL((gemm11_kernel<BK_, C_>), dim3(items), dim3(G11_NT), 0, s, A, B, E, M, N, K, ntn, items,  \
-                         ps.span);                                                                                \
-    break;
-  if (bkc) {
-    switch (code) {
-      TT2_G11(true, 0) TT2_G11(true, 1) TT2_G11(true, 2) TT2_G11(true, 3) TT2_G11(true, 4) TT2_G11(true, 5)
-      TT2_G11(true, 6) TT2_G11(true, 7)
-      default: return hipErrorInvalidValue;
-    }
-  } else {
-    switch (code) {
-      TT2_G11(false, 0) TT2_G11(false, 8) TT2_G11(false, 16)
-      default: return hipErrorInvalidValue;
-    }
-  }
-#undef TT2_G11
-  return hipGetLastError();
-}
-
-// v11's epilogue code for a request (-1: an option set v11 does not fuse): NT forward requests
-// take bias / ReLU / dropout; activation-gradient (trans_b) requests a bf16 residual or gate alone
-int g11_code(const EpiParams& E, bool bkc) {
-  if (E.c_dt != TT2_BF16 || !E.vec || E.beta != 0.f || E.act == ACT_TANH || E.ksum || (E.res && E.gate)) return -1;
-  const int fwd = (E.bias ? 1 : 0) | (E.act == ACT_RELU ? 2 : 0) | (E.drop.thr ? 4 : 0);
-  if (bkc) return (E.res || E.gate) ? -1 : fwd;
-  if (fwd) return -1;
-  if (E.res) return E.res_dt == TT2_BF16 ? 8 : -1;
-  if (E.gate) return E.gate_dt == TT2_BF16 ? 16 : -1;
-  return 0;
-}
-
-int g10_code(const EpiParams& E) {
-  if (E.c_dt != TT2_BF16 || !E.vec || E.beta != 0.f || E.act == ACT_TANH || E.res || E.gate || E.ksum) return -1;
-  return (E.bias ? 1 : 0) | (E.act == ACT_RELU ? 2 : 0) | (E.drop.thr ? 4 : 0);
-}
-
-
-
-
-}  // namespace
 
 extern "C" size_t tt2_gemm_workspace_size(const tt2_gemm_args* a) {
   if (a->splits <= 1) return 0;
@@ -2861,7 +51,8 @@ static bool g7_lds_epi(int variant) { return variant != 13; }
 #ifndef G8_SPLIT_MIN_K   // only the long-K ones (the encoder's K = 2048 products run faster unsplit on v8)
 #define G8_SPLIT_MIN_K 4096
 #endif
-static int gemm_plan(const tt2_gemm_args* a) {
+namespace tt2g {
+int gemm_plan(const tt2_gemm_args* a) {
   const int var = a->kernel_variant;
   const int64_t a_inner = a->trans_a ? a->m : a->k, b_inner = a->trans_b ? a->n : a->k;
   // skinny split-K exists only as raw partial slabs (main_only) for tt2_ln_combine
@@ -2945,8 +136,9 @@ static int gemm_plan(const tt2_gemm_args* a) {
   if ((var == 13 || var == 14 || var == 0) && v7ok) return 13;
   return 2;
 }
+}  // namespace tt2g
 
-extern "C" int tt2_gemm_plan(const tt2_gemm_args* a) { return gemm_plan(a); }
+extern "C" int tt2_gemm_plan(const tt2_gemm_args* a) { return tt2g::gemm_plan(a); }
 
 // Vectorised epilogue: rows of C / res / gate start 16-B aligned at every 8th column.
 static bool epi_vec_ok(const tt2_gemm_args* a) {
@@ -2960,46 +152,55 @@ static bool epi_vec_ok(const tt2_gemm_args* a) {
          (reinterpret_cast<uintptr_t>(a->bias) % 16 == 0);
 }
 
-// The plan tt2_gemm launches: the auto plan, with v8 (which stores C / reads res and gate in
-// 16-B chunks) moved to v7 when those rows are not vector-aligned.  tt2_gemm_stats_rows asks
-// the same function, so the chunk height it reports is the one the kernel writes.
-static int launch_plan(const tt2_gemm_args* a) {
-  int plan = gemm_plan(a);
-  if (plan == 15 && !epi_vec_ok(a)) {
-    tt2_gemm_args b = *a;
-    b.kernel_variant = 13;
-    plan = gemm_plan(&b);
-  }
-  return plan;
+// The route of a request: the kernel that launches (a gemm_plan code; -1: error set), for v10 /
+// v11 its epilogue code, and for a fused-statistics request (col_stats / bn_bwd) the chunk height
+// that kernel writes (0: no kernel of the route can carry the statistics).  It starts from the
+// planner's choice and applies what the planner leaves to the launch:
+//  - v8 stores C and reads res / gate in 16-B chunks: rows that are not vector-aligned take the
+//    forced-v7 plan (v7, or v2);
+//  - fused statistics run on v8 (64-row chunks) when the plan takes it, else on v7's LDS-image
+//    epilogue (256-row chunks: NT, n % 128 == 0, not variant 13); neither can with split-K, f32 C
+//    or unaligned rows;
+//  - an option set v10 / v11 do not fuse takes the forced-v7 plan.  (v10's plan condition implies
+//    every term of g10_code but one: epi_vec_ok also refuses an f16 res_dtype / gate_dtype on a
+//    null res / gate, so that fallback stays.)
+// tt2_gemm switches on the result; tt2_gemm_stats_rows answers from the same call.
+struct Route { int kernel, code, stats_rows; };
+
+static int replan(const tt2_gemm_args* a, int variant) {
+  tt2_gemm_args b = *a;
+  b.kernel_variant = variant;
+  return tt2g::gemm_plan(&b);
 }
 
-// The kernel a fused-statistics request (col_stats / bn_bwd) runs on, given the auto plan: v8
-// (64-row chunks) when the plan takes it, else v7's LDS-image epilogue (256-row chunks); -1 when
-// neither can (split-K, f32 C, unaligned rows, v7 with a transposed operand or n % 128).
-static int stats_plan(const tt2_gemm_args* a, int plan) {
-  auto al = [](const void* p, int64_t ld) { return reinterpret_cast<uintptr_t>(p) % 16 == 0 && (ld * 2) % 16 == 0; };
-  if (a->splits > 1 || a->dtype_out != TT2_BF16 || !al(a->c, a->ldc) || a->n % 8 ||
-      (reinterpret_cast<uintptr_t>(a->col_stats) & 3))
-    return -1;
-  if (plan == 15) return 15;
-  if (plan != 13) {
-    tt2_gemm_args b = *a;
-    b.kernel_variant = 14;
-    plan = gemm_plan(&b);
+static Route gemm_route(const tt2_gemm_args* a, bool stats) {
+  Route r{tt2g::gemm_plan(a), 0, 0};
+  if (r.kernel < 0) return r;
+  const bool vec = epi_vec_ok(a);
+  if (r.kernel == 15 && !vec) r.kernel = replan(a, 13);
+  if (stats) {
+    auto al = [](const void* p, int64_t ld) { return reinterpret_cast<uintptr_t>(p) % 16 == 0 && (ld * 2) % 16 == 0; };
+    bool ok = a->splits <= 1 && a->dtype_out == TT2_BF16 && al(a->c, a->ldc) && a->n % 8 == 0 &&
+              (reinterpret_cast<uintptr_t>(a->col_stats) & 3) == 0;
+    if (ok && r.kernel != 15) {
+      // (a forced-v7 plan that fails leaves the planner's kernel: the caller reports that the
+      // statistics cannot be carried, not the re-plan's own error)
+      ok = (r.kernel == 13 || replan(a, 14) == 13) && !a->trans_a && !a->trans_b &&
+           g7_lds_epi(a->kernel_variant) && a->n % 128 == 0;
+      if (ok) r.kernel = 13;
+    }
+    r.stats_rows = !ok ? 0 : r.kernel == 15 ? 64 : 256;
+    return r;
   }
-  if (plan != 13 || a->trans_a || a->trans_b || !g7_lds_epi(a->kernel_variant) || a->n % 128) return -1;
-  return 13;
+  if (r.kernel == 16 && (r.code = tt2g::g10_code(a, vec)) < 0) r.kernel = replan(a, 13);
+  if (r.kernel == 17 && (r.code = tt2g::g11_code(a, vec)) < 0) r.kernel = replan(a, 13);
+  return r;
 }
 
-extern "C" int32_t tt2_gemm_stats_rows(const tt2_gemm_args* a) {
-  const int plan = launch_plan(a);
-  if (plan < 0) return 0;
-  const int sp = stats_plan(a, plan);
-  return sp == 15 ? 64 : sp == 13 ? 256 : 0;
-}
+extern "C" int32_t tt2_gemm_stats_rows(const tt2_gemm_args* a) { return gemm_route(a, true).stats_rows; }
 
 // Validate one GEMM request and build its operand / epilogue descriptors.
-static int gemm_prep(const tt2_gemm_args* a, OpDesc& A, OpDesc& B, EpiParams& ep) {
+int tt2g::gemm_prep(const tt2_gemm_args* a, Operand& A, Operand& B, Epilogue& ep) {
   const int esz = a->dtype_in == TT2_F32 ? 4 : 2;
   const int E = 16 / esz;
   auto misaligned = [&](const void* p, int64_t ld) {
@@ -3015,13 +216,13 @@ static int gemm_prep(const tt2_gemm_args* a, OpDesc& A, OpDesc& B, EpiParams& ep
   if (a->splits > 1 && (!a->workspace || a->ws_bytes < tt2_gemm_workspace_size(a)))
     return tt2_set_error(TT2_E_INVALID, "tt2_gemm: split-K workspace too small");
 
-  A = OpDesc{a->a, a->lda, 0, 0, a->a_conv_t, a->a_conv_c, a->a_conv_pad};
-  B = OpDesc{a->b, a->ldb, 0, 0, a->b_conv_t, a->b_conv_c, a->b_conv_pad};
+  A = Operand{a->a, a->lda, 0, 0, a->a_conv_t, a->a_conv_c, a->a_conv_pad};
+  B = Operand{a->b, a->ldb, 0, 0, a->b_conv_t, a->b_conv_c, a->b_conv_pad};
   if (!a->trans_a) { A.outer_max = a->m; A.inner_max = a->k; } else { A.outer_max = a->k; A.inner_max = a->m; }
   if (!a->trans_b) { B.outer_max = a->n; B.inner_max = a->k; } else { B.outer_max = a->k; B.inner_max = a->n; }
   if (a->k <= 0) return tt2_set_error(TT2_E_INVALID, "tt2_gemm: k must be > 0");
 
-  ep = EpiParams{};
+  ep = Epilogue{};
   ep.c = a->c; ep.ldc = a->ldc; ep.c_dt = a->dtype_out;
   ep.bias = a->bias;
   ep.res = a->res; ep.ldr = a->ldr; ep.res_dt = a->res_dtype;
@@ -3049,334 +250,43 @@ static int gemm_prep(const tt2_gemm_args* a, OpDesc& A, OpDesc& B, EpiParams& ep
   return TT2_OK;
 }
 
-// An armed launch probe belongs to the next main GEMM launch of this call only: whatever
-// path the call takes, it is disarmed on return (tt2_probe_ms then reports -1 for a slot
-// no probe-capable kernel consumed).
-struct ProbeDisarm {
-  ~ProbeDisarm() { g_probe_armed = -1; }
-};
-
 extern "C" int tt2_gemm(const tt2_gemm_args* a, hipStream_t stream) {
   ProbeDisarm disarm;
   if (a->m <= 0 || a->n <= 0) return TT2_OK;
-  OpDesc A, B;
-  EpiParams ep;
-  if (const int rc = gemm_prep(a, A, B, ep); rc != TT2_OK) return rc;
+  Operand A, B;
+  Epilogue ep;
+  if (const int rc = tt2g::gemm_prep(a, A, B, ep); rc != TT2_OK) return rc;
   float* ws = reinterpret_cast<float*>(a->workspace);
   const int sp = a->splits > 1 ? a->splits : 1;
-
-  hipError_t err;
-  int plan = launch_plan(a);             // v8 stores C in 16-B chunks: unaligned rows take v7 (or v2)
-  if (plan < 0) return TT2_E_INVALID;   // message already set
-  if (ep.cstats || ep.bnb.part) {   // fused BatchNorm statistics: v8's or v7's image epilogue
-    plan = stats_plan(a, plan);
-    if (plan < 0)
+  const bool stats = ep.cstats || ep.bnb.part;   // fused BatchNorm statistics: v8's or v7's image epilogue
+  const Route r = gemm_route(a, stats);
+  if (r.kernel < 0) return TT2_E_INVALID;   // message already set
+  if (stats) {
+    if (!r.stats_rows)
       return tt2_set_error(TT2_E_INVALID, "tt2_gemm: col_stats / bn_bwd need the v8 path or v7's LDS-image path "
                                           "(bf16 C, 16-B aligned rows, no split-K; v7: NT and n % 128 == 0)");
-    const int rp = plan == 15 ? 64 : 256;
+    const int rp = r.stats_rows;
     if (a->bn_bwd && a->bn_bwd->ws_bytes < (size_t)((a->m + rp - 1) / rp) * 2 * a->n * sizeof(float))
       return tt2_set_error(TT2_E_INVALID, "tt2_gemm: bn_bwd workspace smaller than its chunk sums");
   }
-  if (plan == 3) {   // skinny-M weight-streaming path (decode step)
-    SkinnyFuse F{reinterpret_cast<const bf16*>(a->a_ln_branch), a->a_ln_gamma, a->a_ln_beta,
-                 reinterpret_cast<bf16*>(a->a_ln_out), a->a_ln_eps, a->kv_cache, a->kv_t,
-                 a->kv_col0, a->kv_bstride, a->kv_ld, a->pe_table, a->pe_alpha, a->pe_t, a->emit_mel, a->emit_stop,
-                 a->emit_prev, a->emit_t, a->emit_seed, a->emit_done, a->emit_nmels, a->emit_tmax,
-                 a->emit_stop_bias, a->emit_stop_len, a->emit_stop_thr};
-    const size_t lds = a->a_ln_gamma ? 32 * SK_LN_LD * sizeof(bf16) : 0;
-    // split-K (splits > 1, main_only): raw partial slabs [splits][m][n] f32 in the workspace
-    const int sp = a->splits > 1 ? a->splits : 1;
-    const int kper = sp > 1 ? ((a->k + sp - 1) / sp + 31) / 32 * 32 : a->k;
-    float* slab = sp > 1 ? reinterpret_cast<float*>(a->workspace) : nullptr;
-    const dim3 grid((a->n + SK_COLS - 1) / SK_COLS, sp > 1 ? (a->k + kper - 1) / kper : 1);
-    // per-wave K slice = NCH x 32: one pass for K <= 4 * NCH * 32
-    const int nch = kper <= 128 ? 1 : kper <= 256 ? 2 : kper <= 512 ? 4 : kper <= 1024 ? 8 : 16;
-#define TT2_SK(TE, NCH, LN, MR)                                                                              \
-  hipLaunchKernelGGL((gemm_skinny_kernel<TE, NCH, LN, MR>), grid, dim3(NT), lds, stream,                    \
-                     reinterpret_cast<const TE*>(a->a), a->lda, reinterpret_cast<const TE*>(a->b), a->ldb, ep, \
-                     a->m, a->n, a->k, F, slab, kper)
-#define TT2_SK_M(TE, MR)                      \
-  if (nch == 1) TT2_SK(TE, 1, false, MR);     \
-  else if (nch == 2) TT2_SK(TE, 2, false, MR); \
-  else if (nch == 4) TT2_SK(TE, 4, false, MR); \
-  else if (nch == 8) TT2_SK(TE, 8, false, MR); \
-  else if (MR == 2) TT2_SK(TE, 16, false, 2);  \
-  else TT2_SK(TE, 8, false, 4);   /* 64 rows: two passes of 8 chunks (16 would spill) */
-    if (a->a_ln_gamma) TT2_SK(bf16, 4, true, 2);   // bf16, k == 512, m <= 32 (checked by the plan)
-    else if (a->dtype_in == TT2_F16) {
-      if (a->m <= 32) { TT2_SK_M(f16, 2) } else { TT2_SK_M(f16, 4) }
-    } else {
-      if (a->m <= 32) { TT2_SK_M(bf16, 2) } else { TT2_SK_M(bf16, 4) }
-    }
-#undef TT2_SK_M
-#undef TT2_SK
-    return tt2_check_launch(hipGetLastError(), "tt2_gemm(skinny)");
+  const bool a_kc = !a->trans_a, b_kc = !a->trans_b;
+  const int m = a->m, n = a->n, k = a->k;
+  switch (r.kernel) {
+    case 3:   // skinny-M weight-streaming path (decode step)
+      return tt2_check_launch(tt2g::launch_skinny(a, ep, stream), "tt2_gemm(skinny)");
+    case 16:
+      return tt2_check_launch(tt2g::launch10(A, B, ep, m, n, k, r.code, stream), "tt2_gemm(v10)");
+    case 17:
+      return tt2_check_launch(tt2g::launch11(A, B, ep, m, n, k, b_kc, r.code, stream), "tt2_gemm(v11)");
+    case 15:
+      return tt2_check_launch(tt2g::launch8(b_kc, A, B, ep, m, n, k, stream), "tt2_gemm(v8)");
+    case 13:
+      return tt2_check_launch(tt2g::launch7(a_kc, b_kc, A, B, ep, m, n, k, sp, ws, stream,
+                                            g7_lds_epi(a->kernel_variant)), "tt2_gemm(v7)");
+    case 2:
+      return tt2_check_launch(tt2g::launch2(a_kc, b_kc, A, B, ep, m, n, k, sp, ws, stream), "tt2_gemm");
+    default:
+      return tt2_check_launch(tt2g::launch1(a->dtype_in == TT2_BF16, a_kc, b_kc, A, B, ep, m, n, k, sp, ws, stream),
+                              "tt2_gemm");
   }
-  if (plan == 16) {
-    const int code = g10_code(ep);
-    if (code >= 0) return tt2_check_launch(launch10(A, B, ep, a->m, a->n, a->k, code, stream), "tt2_gemm(v10)");
-    tt2_gemm_args b = *a;   // an epilogue v10 does not fuse (unaligned rows, ...): v7
-    b.kernel_variant = 13;
-    plan = gemm_plan(&b);
-  }
-  if (plan == 17) {
-    const int code = g11_code(ep, !a->trans_b);
-    if (code >= 0)
-      return tt2_check_launch(launch11(A, B, ep, a->m, a->n, a->k, !a->trans_b, code, stream), "tt2_gemm(v11)");
-    tt2_gemm_args b = *a;   // an epilogue v11 does not fuse: v7
-    b.kernel_variant = 13;
-    plan = gemm_plan(&b);
-  }
-  if (plan == 15) {
-    if (!a->trans_b) err = launch8<true>(A, B, ep, a->m, a->n, a->k, stream);
-    else err = launch8<false>(A, B, ep, a->m, a->n, a->k, stream);
-    return tt2_check_launch(err, "tt2_gemm(v8)");
-  }
-  if (plan == 13) {
-    const bool le = g7_lds_epi(a->kernel_variant);
-    if (!a->trans_a && !a->trans_b) err = launch7<true, true>(A, B, ep, a->m, a->n, a->k, sp, ws, stream, le);
-    else if (!a->trans_a && a->trans_b) err = launch7<true, false>(A, B, ep, a->m, a->n, a->k, sp, ws, stream, le);
-    else if (a->trans_a && !a->trans_b) err = launch7<false, true>(A, B, ep, a->m, a->n, a->k, sp, ws, stream, le);
-    else err = launch7<false, false>(A, B, ep, a->m, a->n, a->k, sp, ws, stream, le);
-    return tt2_check_launch(err, "tt2_gemm(v7)");
-  }
-  if (plan == 2) {
-    if (!a->trans_a && !a->trans_b) err = launch2<true, true>(A, B, ep, a->m, a->n, a->k, sp, ws, stream);
-    else if (!a->trans_a && a->trans_b) err = launch2<true, false>(A, B, ep, a->m, a->n, a->k, sp, ws, stream);
-    else if (a->trans_a && !a->trans_b) err = launch2<false, true>(A, B, ep, a->m, a->n, a->k, sp, ws, stream);
-    else err = launch2<false, false>(A, B, ep, a->m, a->n, a->k, sp, ws, stream);
-    return tt2_check_launch(err, "tt2_gemm");
-  }
-#define TT2_GEMM_CASE(T)                                                                              \
-  if (!a->trans_a && !a->trans_b) err = launch_t<T, true, true>(A, B, ep, a->m, a->n, a->k, sp, ws, stream);   \
-  else if (!a->trans_a && a->trans_b) err = launch_t<T, true, false>(A, B, ep, a->m, a->n, a->k, sp, ws, stream); \
-  else if (a->trans_a && !a->trans_b) err = launch_t<T, false, true>(A, B, ep, a->m, a->n, a->k, sp, ws, stream); \
-  else err = launch_t<T, false, false>(A, B, ep, a->m, a->n, a->k, sp, ws, stream);
-  if (a->dtype_in == TT2_BF16) { TT2_GEMM_CASE(bf16) } else { TT2_GEMM_CASE(float) }
-#undef TT2_GEMM_CASE
-  return tt2_check_launch(err, "tt2_gemm");
-}
-
-extern "C" int tt2_gemm_grouped_fin(const tt2_gemm_args* probs, int n, const tt2_ln_args* fin,
-                                    hipStream_t stream) {
-  return tt2_gemm_grouped_ex(probs, n, fin, 0, stream);
-}
-
-extern "C" int tt2_gemm_grouped_ex(const tt2_gemm_args* probs, int n, const tt2_ln_args* fin, int max_groups,
-                                   hipStream_t stream) {
-  ProbeDisarm disarm;
-  if (n <= 0 && !fin) return TT2_OK;
-  if ((n > 0 && !probs) || n > G7_MAXP) return tt2_set_error(TT2_E_INVALID, "tt2_gemm_grouped: 1..8 problems");
-  G7Group G{};
-  if (fin && fin->m > 0) {
-    if (!fin->defer_finalize || !fin->workspace || fin->c <= 0)
-      return tt2_set_error(TT2_E_INVALID, "tt2_gemm_grouped_fin: fin must be a deferred LayerNorm backward");
-    G.fin.part = reinterpret_cast<const float*>(fin->workspace);
-    G.fin.dst[0] = fin->dgamma; G.fin.dst[1] = fin->dbeta; G.fin.dst[2] = fin->dbias;
-    G.fin.gb = fin->grad_beta;
-    G.fin.C = fin->c;
-    G.fin.nb = (int)(tt2_layernorm_bwd_workspace_size(fin) / (3 * sizeof(float) * fin->c));
-  }
-  int reduce_blocks = 0, ta = -1, tb = -1, main_only = 1;
-  for (int i = 0; i < n; ++i) {
-    const tt2_gemm_args* a = probs + i;
-    if (a->m <= 0 || a->n <= 0) continue;
-    OpDesc A, B;
-    EpiParams ep;
-    if (const int rc = gemm_prep(a, A, B, ep); rc != TT2_OK) return rc;
-    if (gemm_plan(a) != 13)
-      return tt2_set_error(TT2_E_INVALID, "tt2_gemm_grouped: every problem must take the v7 kernel (bf16, "
-                                          "8-aligned inner dims, conv T, C >= 64, no decode fusions)");
-    if (a->col_stats || a->bn_bwd) return tt2_set_error(TT2_E_INVALID, "tt2_gemm_grouped: no col_stats / bn_bwd");
-    if (ta < 0) { ta = a->trans_a; tb = a->trans_b; }
-    if (a->trans_a != ta || a->trans_b != tb)
-      return tt2_set_error(TT2_E_INVALID, "tt2_gemm_grouped: problems must share trans_a / trans_b");
-    G7Prob P = g7_prob(A, B, ep, a->m, a->n, a->k, a->splits > 1 ? a->splits : 1,
-                       reinterpret_cast<float*>(a->workspace));
-    P.item0 = G.items;
-    G.items += P.items;
-    G.p[G.np++] = P;
-    main_only &= a->main_only;
-    if (P.splits > 1) {
-      reduce_blocks = std::max(reduce_blocks, splitk_blocks(a->m, a->n, ep));
-    }
-  }
-  const int fin_blocks = G.fin.nb ? (3 * G.fin.C + G7_FIN_WAVES - 1) / G7_FIN_WAVES : 0;
-  if (G.np == 0) {
-    G.fin_only = 1;
-    if (fin_blocks) hipLaunchKernelGGL(gemm_splitk_reduce_g, dim3(fin_blocks, 1), dim3(256), 0, stream, G);
-    return tt2_check_launch(hipGetLastError(), "tt2_gemm_grouped");
-  }
-  // max_groups > 0: at most that many work groups at a time (rounded down to a multiple of 8,
-  // >= 8): the items go out as consecutive launches of that many, so a launch beside other
-  // work leaves the rest of the CUs free.  An armed launch probe times the whole sequence: the
-  // span slots of launch i start at item ibase, the eager events ride on the first and last.
-  const int grid = max_groups > 0 ? std::min(G.items, std::max(8, max_groups / 8 * 8)) : G.items;
-  ProbeScope ps(stream, G.items);
-  ps.chunk(grid);
-  for (G.ibase = 0; G.ibase < G.items; G.ibase += grid) {
-    const dim3 g(std::min(grid, G.items - G.ibase));
-    G.p[0].span = ps.span ? ps.span + (size_t)TT2_SPAN_W * G.ibase : nullptr;
-    hipEvent_t ev0 = G.ibase == 0 ? ps.e0 : nullptr, ev1 = G.ibase + grid >= G.items ? ps.e1 : nullptr;
-#define TT2_G7G(A_, B_)                                                                                    \
-  if (ps.ext())                                                                                          \
-    hipExtLaunchKernelGGL((gemm7g_kernel<A_, B_>), g, dim3(G7_NT), 0, stream, ev0, ev1, 0, G);            \
-  else                                                                                                   \
-    hipLaunchKernelGGL((gemm7g_kernel<A_, B_>), g, dim3(G7_NT), 0, stream, G);
-    if (!ta && !tb) { TT2_G7G(true, true) }
-    else if (!ta && tb) { TT2_G7G(true, false) }
-    else if (ta && !tb) { TT2_G7G(false, true) }
-    else { TT2_G7G(false, false) }
-#undef TT2_G7G
-  }
-  G.ibase = 0;
-  G.p[0].span = nullptr;
-  if (main_only) reduce_blocks = 0;
-  G.fin_only = reduce_blocks == 0 && fin_blocks > 0;
-  if (G.fin_only)
-    hipLaunchKernelGGL(gemm_splitk_reduce_g, dim3(fin_blocks, 1), dim3(256), 0, stream, G);
-  else if (reduce_blocks > 0)
-    hipLaunchKernelGGL(gemm_splitk_reduce_g, dim3(std::max(reduce_blocks, fin_blocks), G.np + (fin_blocks ? 1 : 0)),
-                       dim3(256), 0, stream, G);
-  return tt2_check_launch(hipGetLastError(), "tt2_gemm_grouped");
-}
-
-extern "C" int tt2_gemm_grouped(const tt2_gemm_args* probs, int n, hipStream_t stream) {
-  return tt2_gemm_grouped_fin(probs, n, nullptr, stream);
-}
-
-extern "C" int tt2_probe_arm(void) {
-  // timing-only events: no system-scope fence (cache write-back) at the probed kernel's end,
-  // which would lengthen it beyond what it takes inside the step
-  ProbeSlot p{nullptr, nullptr, false};
-  hipError_t e = hipSuccess;
-  if (!g_span) {
-    e = hipMalloc(&g_span, TT2_SPAN_W * sizeof(unsigned long long) * PROBE_SPAN_PAIRS);
-    if (e == hipSuccess) e = hipMemset(g_span, 0, TT2_SPAN_W * sizeof(unsigned long long) * PROBE_SPAN_PAIRS);
-    if (e != hipSuccess) {
-      if (g_span) (void)hipFree(g_span);
-      g_span = nullptr;
-      return tt2_check_launch(e, "tt2_probe_arm (span records)");
-    }
-  }
-  e = hipEventCreateWithFlags(&p.start, hipEventDisableSystemFence);
-  if (e == hipSuccess) e = hipEventCreateWithFlags(&p.stop, hipEventDisableSystemFence);
-  if (e != hipSuccess) return tt2_check_launch(e, "tt2_probe_arm");
-  g_probe.push_back(p);
-  g_span_rec.push_back({-1, 0});
-  g_span_chunk.push_back(0);
-  g_probe_armed = (int)g_probe.size() - 1;
-  return g_probe_armed;
-}
-
-extern "C" float tt2_probe_ms(int slot) {
-  if (slot < 0 || slot >= (int)g_probe.size() || !g_probe[slot].used) return -1.f;
-  float ms = -1.f;
-  if (hipEventSynchronize(g_probe[slot].stop) != hipSuccess) return -1.f;
-  if (hipEventElapsedTime(&ms, g_probe[slot].start, g_probe[slot].stop) != hipSuccess) return -1.f;
-  return ms;
-}
-
-extern "C" float tt2_probe_span_ms(int slot) {
-  if (slot < 0 || slot >= (int)g_probe.size() || !g_probe[slot].used || g_span_rec[slot].first < 0) return -1.f;
-  const int64_t off = g_span_rec[slot].first;
-  const int groups = g_span_rec[slot].second;
-  std::vector<unsigned long long> h(TT2_SPAN_W * (size_t)groups);
-  if (hipDeviceSynchronize() != hipSuccess) return -1.f;
-  if (hipMemcpy(h.data(), g_span + TT2_SPAN_W * off, h.size() * 8, hipMemcpyDeviceToHost) != hipSuccess) return -1.f;
-  // zeroed again, so the next replay of a graph must record every pair afresh
-  if (hipMemset(g_span + TT2_SPAN_W * off, 0, h.size() * 8) != hipSuccess) return -1.f;
-  const int chunk = g_span_chunk[slot] > 0 ? g_span_chunk[slot] : groups;
-  unsigned long long total = 0;
-  for (int c0 = 0; c0 < groups; c0 += chunk) {   // each launch's own span
-    unsigned long long t0 = ~0ull, t1 = 0;
-    for (int i = c0; i < std::min(groups, c0 + chunk); ++i) {
-      const unsigned long long s0 = h[TT2_SPAN_W * i], s1 = h[TT2_SPAN_W * i + 1];
-      if (s0 == 0 || s1 < s0) return -1.f;   // a work group left no record
-      t0 = std::min(t0, s0);
-      t1 = std::max(t1, s1);
-    }
-    total += t1 - t0;
-  }
-  static int khz = 0;
-  if (!khz) {
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, dev) != hipSuccess || khz <= 0) {
-      khz = 0;
-      return -1.f;
-    }
-  }
-  return (float)((double)total / khz);
-}
-
-extern "C" int tt2_probe_span_records(int slot, unsigned long long* out, int cap) {
-  if (slot < 0 || slot >= (int)g_probe.size() || !g_probe[slot].used || g_span_rec[slot].first < 0 || !out)
-    return -1;
-  const int64_t off = g_span_rec[slot].first;
-  const int groups = g_span_rec[slot].second;
-  if (cap < groups) return -groups - 1;
-  if (hipDeviceSynchronize() != hipSuccess) return -1;
-  if (hipMemcpy(out, g_span + TT2_SPAN_W * off, (size_t)groups * TT2_SPAN_W * 8, hipMemcpyDeviceToHost) != hipSuccess)
-    return -1;
-  return groups;
-}
-
-// u64 slots per work group in tt2_probe_span_records' output: 2 ({start, end} on the wall
-// clock), 32 in the in-step phase build (TT2_PHASE, see TT2_SPAN_W)
-extern "C" int tt2_probe_span_width(void) { return TT2_SPAN_W; }
-
-extern "C" void tt2_probe_reset(void) {
-  // records of slots never read are zeroed so the pool can be handed out again
-  if (g_span && g_span_used) (void)hipMemset(g_span, 0, TT2_SPAN_W * sizeof(unsigned long long) * g_span_used);
-  g_span_used = 0;
-  g_span_rec.clear();
-  g_span_chunk.clear();
-  for (ProbeSlot& p : g_probe) {
-    (void)hipEventDestroy(p.start);
-    (void)hipEventDestroy(p.stop);
-  }
-  g_probe.clear();
-  g_probe_armed = -1;
-}
-
-// The decode step's FFN sublayer in one launch (ffn_decode_kernel above).
-static int ffn_decode(const tt2_ffn_decode_args* a, uint64_t* stamps, hipStream_t s) {
-  if (!a) return tt2_set_error(TT2_E_INVALID, "tt2_ffn_decode: null arguments");
-  if (a->m <= 0) return TT2_OK;
-  if (a->m > 64 || a->d_model != FFN_D || a->d_ffn != FFN_F)
-    return tt2_set_error(TT2_E_INVALID, "tt2_ffn_decode: m <= 64, d_model 512 and d_ffn 2048");
-  if (a->dtype != TT2_DT_BF16 && a->dtype != TT2_DT_F16)
-    return tt2_set_error(TT2_E_INVALID, "tt2_ffn_decode: dtype bf16 or f16");
-  if (!a->x || !a->w1 || !a->b1 || !a->w2 || !a->b2 || !a->gamma || !a->beta || !a->hidden || !a->slab ||
-      !a->sync || !a->y)
-    return tt2_set_error(TT2_E_INVALID, "tt2_ffn_decode: null buffer");
-  const void* vec[] = {a->x, a->w1, a->w2, a->hidden, a->y, a->slab, a->gamma, a->beta, a->b1, a->b2};
-  for (const void* p : vec)
-    if (reinterpret_cast<uintptr_t>(p) % 16)
-      return tt2_set_error(TT2_E_INVALID, "tt2_ffn_decode: buffers must be 16-B aligned");
-  if (reinterpret_cast<uintptr_t>(a->sync) % 4) return tt2_set_error(TT2_E_INVALID, "tt2_ffn_decode: sync alignment");
-#define TT2_FFN(TE, MR)                                                                                             \
-  {                                                                                                                 \
-    FfnArgs<TE> f{reinterpret_cast<const TE*>(a->x), reinterpret_cast<const TE*>(a->w1), a->b1,                  \
-                  reinterpret_cast<const TE*>(a->w2), a->b2, a->gamma, a->beta, reinterpret_cast<TE*>(a->hidden), \
-                  a->slab, a->sync, reinterpret_cast<TE*>(a->y), a->m, a->eps, stamps};                          \
-    hipLaunchKernelGGL((ffn_decode_kernel<TE, MR>), dim3(FFN_WG), dim3(NT), 0, s, f);                           \
-  }
-  if (a->dtype == TT2_DT_F16) {
-    if (a->m <= 32) TT2_FFN(f16, 2) else TT2_FFN(f16, 4)
-  } else {
-    if (a->m <= 32) TT2_FFN(bf16, 2) else TT2_FFN(bf16, 4)
-  }
-#undef TT2_FFN
-  return tt2_check_launch(hipGetLastError(), "tt2_ffn_decode");
-}
-
-extern "C" int tt2_ffn_decode(const tt2_ffn_decode_args* a, hipStream_t s) { return ffn_decode(a, nullptr, s); }
-
-// Measurement hook: tt2_ffn_decode that also writes 8 wall-clock stamps per work group to
-// stamps[256][8] (entry, hidden stored, hidden counted, K slice ready, slab stored, slab
-// counted, rows ready, exit).
-extern "C" int tt2_ffn_decode_stamps(const tt2_ffn_decode_args* a, uint64_t* stamps, hipStream_t s) {
-  return ffn_decode(a, stamps, s);
 }

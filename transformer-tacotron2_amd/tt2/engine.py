@@ -41,7 +41,7 @@ def sinusoid_table(max_len: int, dim: int) -> torch.Tensor:
 def _wide(dtype, conv, m: int, *inner: int) -> bool:
     """True when tt2_gemm's auto plan takes the 256 x 128 kernel (v7) for a GEMM with
     m output rows: bf16, 8-aligned inner dims, conv operands (T, C, pad) with T, C >= 64,
-    not the skinny decode path (see gemm.hip gemm_plan)."""
+    not the skinny decode path (see gemm_plan in csrc/gemm.hip)."""
     conv_ok = conv is None or (conv[0] >= 64 and conv[1] >= 64)
     return dtype == torch.bfloat16 and conv_ok and m > 32 and all(d % 8 == 0 for d in inner)
 
