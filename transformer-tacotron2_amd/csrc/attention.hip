@@ -258,6 +258,12 @@ __global__ __launch_bounds__(NT) void attn_fwd_kernel(ArgsT<G> a) {
 }
 
 // ---------------------------------------------------------------- backward
+// a * b rounded once, never contracted into a following add or subtract
+TT2_DEV float mul_rn(float a, float b) {
+#pragma clang fp contract(off)
+  return a * b;
+}
+
 // delta[bh, t] = sum_d dO[t, h*64 + d] * O[t, h*64 + d]; one wave per (b, t) row, all heads.
 // G: delta + kappa g for the guided rows, so dS = P (dP + kappa W - delta) downstream
 template <typename T, bool G>
@@ -372,7 +378,9 @@ __global__ __launch_bounds__(NT) void attn_bwd_dq_kernel(ArgsT<G> a) {
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const int qr = q0 + 16 * w + 4 * hq + r;
-        float p = exp2f(s[jb][r] * c - lse[r]);
+        // the product rounded as the forward rounded it (its max and LSE come from RN(s c)): left to
+        // contract into fma(s, c, -lse), P comes back off by ulp(s c) / 2, 4e-5 at a score of 2000
+        float p = exp2f(mul_rn(s[jb][r], c) - lse[r]);
         if (key >= klim || (a.causal && key > qr)) p = 0.f;
         float ds;
         if (G && gd.sel) ds = p * (fmaf(kap[r], guide_w<false>((float)key * gd.rk, nq[r], gk), dp[jb][r]) - dl[r]);
@@ -486,7 +494,7 @@ __global__ __launch_bounds__(NT) void attn_bwd_dkdv_kernel(ArgsT<G> a) {
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const int key = k0 + 16 * w + 4 * hq + r;
-        float p = exp2f(s[jb][r] * c - lse[jb]);
+        float p = exp2f(mul_rn(s[jb][r], c) - lse[jb]);   // RN(s c) as in the forward (see attn_bwd_dq_kernel)
         if (key >= klim || (a.causal && key > qc) || qc >= a.Tq) p = 0.f;
         pv[jb][r] = p;
         myP[(4 * hq + r) * LD + 16 * jb + row_l] = from_f32<T>(p);
