@@ -302,6 +302,51 @@ typedef struct tt2_align_dur_args {
 } tt2_align_dur_args;
 int tt2_align_durations(const tt2_align_dur_args* a, hipStream_t stream);
 
+/* Monotonic alignment search (Viterbi over the raw scores of forwards already run; no attention
+ * matrix is stored).  One work group per utterance.  For utterance b the (layer slot, head) is
+ * sel[2b], sel[2b+1] read on the device (as tt2_align_durations writes it), or sel_layer /
+ * sel_head when sel is NULL.  With Ty = clamp(q_len[b], 0, tq), Tx = clamp(key_len[b], 0, tk),
+ * Te = min(Tx, Ty) and s[n, t] the unscaled f32 score q_n . k_t (bf16, variant 0: the v3 forward's
+ * MFMA sequence; f32 or variant 1: tt2_attn_align's scalar dot), the path pi maximises
+ * sum_n s[n, pi(n)] over pi(0) = 0, pi(Ty-1) = Te-1, pi(n+1) - pi(n) in {0, 1}:
+ *   V[0][0] = s[0][0], V[0][t>0] = -inf, V[n][t] = s[n][t] + max(V[n-1][t], V[n-1][t-1]),
+ *   move[n][t] = V[n-1][t-1] > V[n-1][t]   (strict: a tie stays on the same key),
+ *   backtrack from (Ty-1, Te-1): pi(n-1) = pi(n) - move[n][pi(n)].
+ * Every row's log-sum-exp is common to all paths and scale > 0, so this is the maximum-likelihood
+ * monotone path of log P.  Outputs:
+ *   path[b][n]      = pi(n) for n < Ty, -1 for n >= Ty
+ *   durations[b][t] = #{n : pi(n) = t}  (0 for t >= Te; the row sums to Ty; >= 1 for every t < Tx
+ *                     when Ty >= Tx)
+ *   logp[b]         = mean over n < Ty of ln 2 * (s[n, pi(n)] * scale * log2(e) - lse[n])  (f32,
+ *                     fixed summation order)
+ * Ty = 0, Tx = 0 or a sel entry outside [0, n_layers) x [0, heads) gives path = -1, durations = 0
+ * and logp = 0 for that utterance (nothing is read through such an entry).  Results are
+ * bit-identical run to run (integer counts, no floating-point atomics).
+ * Limits: head_dim 64, non-causal, scale > 0, 1..16 layers, tk <= TT2_MONO_MAX_KEYS,
+ * tq <= TT2_MONO_MAX_FRAMES, leading dims and the 2 GiB span as in tt2_attn_align.  The move bits
+ * (tq rows of C/32 words, C = tk rounded up to 128, 256 or 512) stay in LDS when they fit;
+ * otherwise they go to `workspace` (8-B aligned, tt2_align_monotonic_workspace_size bytes, which is
+ * 0 when LDS suffices); a smaller workspace is refused (TT2_E_INVALID).
+ * variant: 0 auto (bf16: MFMA score producer, f32: plain), 1 the plain scalar-dot producer. */
+#define TT2_MONO_MAX_KEYS 512
+#define TT2_MONO_MAX_FRAMES 4096
+typedef struct tt2_align_mono_args {
+  const void* q[TT2_GUIDE_MAX_LAYERS];      /* as tt2_align_args */
+  const void* k[TT2_GUIDE_MAX_LAYERS];
+  const float* lse[TT2_GUIDE_MAX_LAYERS];
+  int64_t q_ld, k_ld;
+  const int32_t* key_len; const int32_t* q_len;   /* [batch], device (NULL: tk / tq) */
+  const int32_t* sel;      /* [batch, 2] (layer slot, head), device (NULL: sel_layer / sel_head) */
+  int32_t* path;           /* [batch, tq] int32 */
+  int32_t* durations;      /* [batch, tk] int32 */
+  float* logp;             /* [batch] f32 */
+  void* workspace; size_t workspace_bytes;
+  int32_t n_layers, batch, heads, head_dim, tq, tk, dtype, causal, sel_layer, sel_head, variant;
+  float scale;
+} tt2_align_mono_args;
+size_t tt2_align_monotonic_workspace_size(int batch, int tq, int tk);
+int tt2_align_monotonic(const tt2_align_mono_args* a, hipStream_t stream);
+
 /* ------------------------------------------------------------------ decode
  * One query row per batch element (the AR decode step):
  * out[b*o_ld + 64h ..] = softmax(scale q k^T) v over keys j < n_b of batch b,

@@ -6,7 +6,7 @@ utterance and a durations.json manifest in --out.  The durations are the trainin
 non-autoregressive student (the FastSpeech teacher procedure).
 
     python tools/extract_durations.py --data /data/LJSpeech-1.1 --checkpoint train.pt --out durations/ \
-        [--head best | dataset | L,H] [--batch 16] [--dtype bf16] [--limit N]
+        [--head best | dataset | L,H] [--method argmax | monotonic] [--batch 16] [--dtype bf16] [--limit N]
 
 Every batch has its own (B, Tx, Ty); extract_durations runs each as a transient shape, so the
 engine does not keep an arena of activations per batch.
@@ -36,6 +36,9 @@ def main():
     ap.add_argument("--checkpoint", required=True)
     ap.add_argument("--out", required=True)
     ap.add_argument("--head", type=parse_head, default="best", help='"best" (per utterance), "dataset" or "L,H"')
+    ap.add_argument("--method", choices=("argmax", "monotonic"), default="argmax",
+                    help="argmax histogram (TransformerTTS.durations) or monotonic alignment search "
+                         "(TransformerTTS.monotonic_durations)")
     ap.add_argument("--batch", type=int, default=16)
     ap.add_argument("--dtype", choices=("bf16", "f32"), default="bf16")
     ap.add_argument("--limit", type=int, default=0, help="only the first N utterances (0: all)")
@@ -62,7 +65,7 @@ def main():
                 text, text_len, mel, mel_len = collate(ds, idx, mx)
                 yield [ds.items[i][0] for i in idx], text, text_len.int(), mel, mel_len.int()
 
-    man = extract_durations(model, Batches(), a.out, head=a.head)
+    man = extract_durations(model, Batches(), a.out, head=a.head, method=a.method)
     print(json.dumps({"out": a.out, "utterances": len(man["utterances"]), "head": man["head"],
                       "dataset_head": man.get("dataset_head"),
                       "mean_focus": sum(u["focus"] for u in man["utterances"].values()) / max(1, len(man["utterances"]))}))

@@ -22,7 +22,8 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-I" + INCLUDE, 
          "-Wno-unused-result"]
 # Per-file extras.  Attention keeps MFMA accumulators in arch VGPRs: its softmax reads
 # and rescales them every tile, and the default AGPR placement adds a copy per use.
-EXTRA = {"attention.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"]}
+EXTRA = {"attention.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"],
+         "attention_mono.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"]}
 
 
 def _headers_mtime() -> float:

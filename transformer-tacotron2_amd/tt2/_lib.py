@@ -209,6 +209,28 @@ SIGNATURES.update({
 })
 
 
+MONO_MAX_KEYS = 512      # TT2_MONO_MAX_KEYS
+MONO_MAX_FRAMES = 4096   # TT2_MONO_MAX_FRAMES
+
+
+class AlignMonoArgs(C.Structure):
+    """tt2_align_mono_args: monotonic alignment search over one (layer slot, head) per utterance."""
+    _fields_ = [
+        ("q", vp * GUIDE_MAX_LAYERS), ("k", vp * GUIDE_MAX_LAYERS), ("lse", vp * GUIDE_MAX_LAYERS),
+        ("q_ld", i64), ("k_ld", i64), ("key_len", vp), ("q_len", vp), ("sel", vp),
+        ("path", vp), ("durations", vp), ("logp", vp), ("workspace", vp), ("workspace_bytes", sz),
+        ("n_layers", i32), ("batch", i32), ("heads", i32), ("head_dim", i32), ("tq", i32), ("tk", i32),
+        ("dtype", i32), ("causal", i32), ("sel_layer", i32), ("sel_head", i32), ("variant", i32),
+        ("scale", f32),
+    ]
+
+
+SIGNATURES.update({
+    "tt2_align_monotonic_workspace_size": ([C.c_int, C.c_int, C.c_int], C.c_size_t),
+    "tt2_align_monotonic": ([C.POINTER(AlignMonoArgs), vp], C.c_int),
+})
+
+
 class ReduceArgs(C.Structure):
     _fields_ = [("src", vp), ("dst", vp), ("ld", i64), ("rows", i32), ("cols", i32), ("beta", f32)]
 

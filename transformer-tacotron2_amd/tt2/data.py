@@ -132,7 +132,7 @@ def collate(ds: LJSpeech, indices, extractor, device="cuda"):
     return text.to(device), text_len.to(device), mel, frames.to(torch.long)
 
 
-def extract_durations(model, batches, out_dir: str, head="best"):
+def extract_durations(model, batches, out_dir: str, head="best", method="argmax"):
     """Phoneme durations of every utterance in `batches`, an iterable (re-iterable for
     head="dataset") of (ids, text, text_len, mel, mel_len), through
     model.durations(text, text_len, mel, mel_len, head=...).  head:
@@ -146,6 +146,13 @@ def extract_durations(model, batches, out_dir: str, head="best"):
     Returns the manifest.  The model needs only durations() (and alignment_stats() for
     "dataset"), so a stub drives it in tests.
 
+    method="argmax" (the default) counts each frame's strongest phoneme (model.durations());
+    method="monotonic" takes the durations of the monotonic alignment search instead
+    (model.monotonic_durations(): every phoneme gets a frame when frames >= phonemes, and the
+    frames never go back).  The manifest then carries "method", per utterance the path's "logp"
+    and "min_duration" (0 marks an utterance with fewer frames than phonemes).  The head="dataset"
+    pass that picks the head is the same for both.
+
     Batch shapes: the engine keeps one arena of activations per distinct (B, Tx, Ty) it has run,
     for good (about 110 KB per decoder row in bf16: about 1.1 GB at B = 16 and 650 frames), and
     ragged batches as bucket_batches + collate make them nearly all differ: a corpus would hold
@@ -155,6 +162,9 @@ def extract_durations(model, batches, out_dir: str, head="best"):
     ran (its training shape, a captured step's) is left alone.  The batches are not padded or
     otherwise changed: padding an utterance further changes what the encoder's convolutions see
     at its end, and with it the alignment."""
+    if method not in ("argmax", "monotonic"):
+        raise ValueError(f'extract_durations: method must be "argmax" or "monotonic", got {method!r}')
+    mono = method == "monotonic"
     os.makedirs(out_dir, exist_ok=True)
     use = head
     dataset_focus = None
@@ -183,8 +193,12 @@ def extract_durations(model, batches, out_dir: str, head="best"):
     if dataset_focus is not None:
         manifest["dataset_head"] = list(use)
         manifest["dataset_focus"] = dataset_focus
+    if mono:
+        manifest["method"] = method
     for ids, text, text_len, mel, mel_len in batches:
-        r = model.durations(text, text_len, mel, mel_len, head=use, transient=True)
+        run = model.monotonic_durations if mono else model.durations
+        r = run(text, text_len, mel, mel_len, head=use, transient=True)
+        lp = r.logp.cpu().numpy() if mono else None
         dur, hd, fc = r.durations.cpu().numpy(), r.head.cpu().numpy(), r.focus.cpu().numpy()
         tl = [int(x) for x in torch.as_tensor(text_len).cpu()]
         ml = [int(x) for x in torch.as_tensor(mel_len).cpu()]
@@ -193,6 +207,8 @@ def extract_durations(model, batches, out_dir: str, head="best"):
             np.save(os.path.join(out_dir, f"{uid}.npy"), d)
             manifest["utterances"][str(uid)] = {"layer": int(hd[b, 0]), "head": int(hd[b, 1]), "focus": float(fc[b]),
                                                 "frames": min(ml[b], mel.shape[1]), "phonemes": tl[b]}
+            if mono:
+                manifest["utterances"][str(uid)].update(logp=float(lp[b]), min_duration=int(d.min()) if d.size else 0)
     with open(os.path.join(out_dir, "durations.json"), "w") as f:
         json.dump(manifest, f, indent=1, sort_keys=True)
     return manifest

@@ -436,6 +436,26 @@ class TTSEngine:
                             n, B, H, Ty, Tx, key_len=A["text_len"], q_len=A["mel_len"], head=head)
         return out
 
+    def align_monotonic(self, A: "Arena", layers: tuple, head=None) -> dict:
+        """align_stats (head choice and focus), then tt2_align_monotonic for the chosen head of
+        each utterance, read from `sel` on the device: three launches on the current stream, no
+        host synchronisation, results outside the arena.  Adds path [B, Ty] int32 (-1 past
+        mel_len), logp [B] f32 and replaces durations by the monotone path's."""
+        c = self.cfg
+        d, H = c.d_model, c.n_heads
+        B, Tx, Ty = A.B, A.Tx, A.Ty
+        out = self.align_stats(A, layers, head=head)
+        out["argmax_durations"] = out["durations"]
+        out["path"] = torch.empty(B, Ty, dtype=torch.int32, device=self.dev)
+        out["durations"] = torch.empty(B, Tx, dtype=torch.int32, device=self.dev)
+        out["logp"] = torch.empty(B, dtype=torch.float32, device=self.dev)
+        mkv = A["mkv"]
+        ops.align_monotonic([A[f"dcq{l}"] for l in layers], [mkv[:, 2 * d * l:] for l in layers],
+                            [A[f"dclse{l}"] for l in layers], out["path"], out["durations"], out["logp"],
+                            d, c.n_dec * 2 * d, B, H, Ty, Tx, key_len=A["text_len"], q_len=A["mel_len"],
+                            sel=out["sel"], scale=1.0 / math.sqrt(c.head_dim), ws=self.ws)
+        return out
+
     # ------------------------------------------------------------ GEMM helpers
     def _lin(self, x, w, out, m, n, k, bias=None, act=ACT_NONE, drop=NO_DROP, res=None, ldx=None, ldo=None,
              a_conv=None, beta=0.0, **fuse):

@@ -57,6 +57,15 @@ class Durations(NamedTuple):
     focus: torch.Tensor       # [B] f32: that head's focus rate
 
 
+class MonotonicAlignment(NamedTuple):
+    """monotonic_durations(): the most likely monotone path through the chosen head's attention."""
+    durations: torch.Tensor   # [B, Tx] int32: frames per phoneme; rows sum to mel_len; >= 1 where mel_len >= text_len
+    path: torch.Tensor        # [B, Ty] int32: the phoneme of each frame, non-decreasing (-1 past mel_len)
+    head: torch.Tensor        # [B, 2] int32: the (decoder layer, head) used for each utterance
+    focus: torch.Tensor       # [B] f32: that head's focus rate
+    logp: torch.Tensor        # [B] f32: mean over the frames of ln P[n, path[n]]
+
+
 class _TTSForward(torch.autograd.Function):
     """Teacher-forced forward as one autograd node; backward = the engine's backward from
     the output gradients (it rewrites the flat gradient buffer; a copy is handed to
@@ -469,13 +478,20 @@ class TransformerTTS(nn.Module):
         good (it lives on as the last forward until the next one).  A corpus of ragged batches,
         each of its own shape, would otherwise keep one arena per batch
         (tt2.data.extract_durations passes it).  Arenas that existed before the call stay."""
+        r, sel = self._teacher_alignment("durations", text, text_len, mel, mel_len, head, layers, transient, False)
+        return Durations(r["durations"], sel, r["sel_focus"])
+
+    def _teacher_alignment(self, who, text, text_len, mel, mel_len, head, layers, transient, monotonic):
+        """The shared part of durations() and monotonic_durations(): the teacher-forced forward
+        with dropout off and every piece of training state left alone, then the engine's
+        alignment launches.  Returns the engine's result and sel [B, 2] = (decoder layer, head)."""
         e = self.engine
         ls = e.align_layers(layers)
         fixed = None
         if not (isinstance(head, str) and head == "best"):
             l, h = int(head[0]) % self.cfg.n_dec, int(head[1])
             if l not in ls or not 0 <= h < self.cfg.n_heads:
-                raise ValueError(f"durations: head {tuple(head)} is outside layers {ls} / {self.cfg.n_heads} heads")
+                raise ValueError(f"{who}: head {tuple(head)} is outside layers {ls} / {self.cfg.n_heads} heads")
             fixed = (ls.index(l), h)
         shape = (text.shape[0], text.shape[1], mel.shape[1])
         fresh = transient and shape not in e.arenas
@@ -488,7 +504,7 @@ class TransformerTTS(nn.Module):
         finally:
             e.pipeline_opt = pipelined
             self.train(was_training)
-        r = e.align_stats(A, ls, head=fixed)
+        r = e.align_monotonic(A, ls, head=fixed) if monotonic else e.align_stats(A, ls, head=fixed)
         if fresh:
             e.arenas.pop(shape, None)   # (self._last keeps A until the next forward)
         sel = r["sel"]
@@ -497,7 +513,21 @@ class TransformerTTS(nn.Module):
             if lut is None:
                 lut = self._align_lut[ls] = torch.tensor(ls, dtype=torch.int32, device=e.dev)
             sel = torch.stack((lut[sel[:, 0].long()], sel[:, 1]), dim=1)
-        return Durations(r["durations"], sel, r["sel_focus"])
+        return r, sel
+
+    def monotonic_durations(self, text, text_len, mel, mel_len, head="best", layers=None,
+                            transient=False) -> MonotonicAlignment:
+        """Phoneme durations from a monotonic alignment search (Viterbi over the chosen head's
+        attention scores, as Glow-TTS's MAS): the same forward, head choice and state handling as
+        durations(), but the frames follow the most likely path that starts on the first phoneme,
+        ends on phoneme min(text_len, mel_len) - 1 and advances by 0 or 1 phoneme per frame (on a
+        tie it stays).  Every phoneme gets at least one frame when mel_len >= text_len, the rows
+        sum to mel_len, and `path` expands directly into a length regulator's index sequence.
+        One extra launch after durations()' two; no host synchronisation.  Needs
+        Tx <= 512 phonemes and Ty <= 4096 frames."""
+        r, sel = self._teacher_alignment("monotonic_durations", text, text_len, mel, mel_len, head, layers,
+                                         transient, True)
+        return MonotonicAlignment(r["durations"], r["path"], sel, r["sel_focus"], r["logp"])
 
     # ------------------------------------------------------------ training
     def configure_optimizer(self, **kw):

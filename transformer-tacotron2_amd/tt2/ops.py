@@ -504,6 +504,56 @@ def align_durations(pmax, amax, focus, sel, sel_focus, durations, n_layers, batc
     return durations
 
 
+def align_monotonic(qs, ks, lses, path, durations, logp, q_ld, k_ld, batch, heads, tq, tk, key_len=None,
+                    q_len=None, sel=None, head=None, scale=0.125, variant=None, ws=None):
+    """Monotonic alignment search (tt2_align_mono_args) over the raw scores of forwards already
+    run: per utterance the monotone path through one head's scores with the greatest sum, into
+    path [batch, tq] int32 (-1 past q_len), durations [batch, tk] int32 and logp [batch] f32 (mean
+    ln P along the path).  The head is sel [batch, 2] = (layer slot, head) on the device, as
+    align_durations writes it, or head=(slot, h) for every utterance.  variant: None / 0 auto (bf16:
+    MFMA score producer, f32: plain), 1 the plain scalar-dot producer.  Deterministic."""
+    n = len(qs)
+    if not 1 <= n <= _lib.GUIDE_MAX_LAYERS:
+        raise _lib.TT2Error(f"align_monotonic: 1..{_lib.GUIDE_MAX_LAYERS} layers")
+    if len(ks) != n or len(lses) != n:
+        raise _lib.TT2Error("align_monotonic: one q, k and lse per layer")
+    if (sel is None) == (head is None):
+        raise _lib.TT2Error("align_monotonic: give either sel or head")
+    a = _lib.AlignMonoArgs()
+    hd = heads * 64
+    cd = qs[0].dtype
+    if cd not in (torch.bfloat16, torch.float32):
+        raise _lib.TT2Error(f"align_monotonic: q / k must be bf16 or f32, got {cd}")
+    for i in range(n):
+        _need(f"align_monotonic: q[{i}]", qs[i], _span(q_ld, batch * tq, hd), cd)
+        _need(f"align_monotonic: k[{i}]", ks[i], _span(k_ld, batch * tk, hd), cd)
+        _need(f"align_monotonic: lse[{i}]", lses[i], batch * heads * tq, torch.float32)
+        a.q[i], a.k[i], a.lse[i] = qs[i].data_ptr(), ks[i].data_ptr(), lses[i].data_ptr()
+    _need("align_monotonic: path", path, batch * tq, torch.int32)
+    _need("align_monotonic: durations", durations, batch * tk, torch.int32)
+    _need("align_monotonic: logp", logp, batch, torch.float32)
+    for name, t in (("key_len", key_len), ("q_len", q_len)):
+        if t is not None:
+            _need(f"align_monotonic: {name}", t, batch, torch.int32)
+    if sel is not None:
+        _need("align_monotonic: sel", sel, 2 * batch, torch.int32)
+    else:
+        a.sel_layer, a.sel_head = int(head[0]), int(head[1])
+    a.q_ld, a.k_ld, a.key_len, a.q_len, a.sel = q_ld, k_ld, ptr(key_len), ptr(q_len), ptr(sel)
+    a.path, a.durations, a.logp = path.data_ptr(), durations.data_ptr(), logp.data_ptr()
+    a.n_layers, a.batch, a.heads, a.head_dim, a.tq, a.tk = n, batch, heads, 64, tq, tk
+    a.dtype = _lib.DT_BF16 if cd == torch.bfloat16 else _lib.DT_F32
+    a.causal, a.scale = 0, scale
+    a.variant = 0 if variant is None else variant
+    L = lib()
+    need = L.tt2_align_monotonic_workspace_size(batch, tq, tk)
+    if need:
+        buf = (ws or _WS).get(need)
+        a.workspace, a.workspace_bytes = buf.data_ptr(), buf.numel()
+    check(L.tt2_align_monotonic(C.byref(a), stream_ptr()), "tt2_align_monotonic")
+    return path, durations, logp
+
+
 def _drop_into(s, drop: Drop):
     s.drop_seed, s.drop_site, s.drop_thr, s.drop_scale = drop.fields()
 
