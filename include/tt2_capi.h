@@ -347,6 +347,46 @@ typedef struct tt2_align_mono_args {
 size_t tt2_align_monotonic_workspace_size(int batch, int tq, int tk);
 int tt2_align_monotonic(const tt2_align_mono_args* a, hipStream_t stream);
 
+/* Dynamic time warping between two feature sequences per utterance (the alignment under
+ * mel-cepstral distortion, MCD-DTW).  One work group per utterance pair.  For utterance b with
+ * Na = clamp(a_len[b], 0, ta) and Nb = clamp(b_len[b], 0, tb):
+ *   cost        c[i][j] = sqrt(sum_{k=c0}^{c1-1} (a[i][k] - b[j][k])^2), formed from the differences
+ *               in f32 with an IEEE-rounded square root (a perfect square comes out exact);
+ *   recurrence  D[0][0] = c[0][0], otherwise D[i][j] = c[i][j] + min over the existing predecessors
+ *               (i-1, j-1), (i-1, j), (i, j-1), in f32 with one add per cell.  The predecessor is the
+ *               diagonal if its D is <= both others, else up (i-1, j) if its D is <= left's, else
+ *               left: a tie prefers diagonal, then up, then left;
+ *   total[b]    = D[Na-1][Nb-1];
+ *   length[b]   = L, the number of cells on the path that follows the chosen predecessors back from
+ *               (Na-1, Nb-1) to (0, 0); max(Na, Nb) <= L <= Na + Nb - 1.  It is carried through the
+ *               recurrence beside D, so without a path no move bits and no workspace are needed;
+ *   path        (when path_a and path_b are given) path_a[b][k], path_b[b][k] for k < L are the
+ *               path's cells in forward order, (0, 0) first and (Na-1, Nb-1) last; entries from L
+ *               up to ta + tb - 2 are -1.
+ * Na = 0 or Nb = 0 gives total 0, length 0 and a path of -1; nothing is read through that
+ * utterance's pointers.  Only rows < Na / Nb and columns [c0, c1) of a and b are read.  Results
+ * are bit-identical run to run (no floating-point atomics, no hand-off between work groups).
+ * The path needs `workspace` (4-B aligned) of tt2_dtw_workspace_size bytes for the move codes:
+ * 2 bits per cell, 16 rows of one column per word.  The size is 0 without a path or with a zero
+ * dimension.  Refused with TT2_E_INVALID before any launch: ta or tb > TT2_DTW_MAX_FRAMES or < 0,
+ * c1 - c0 outside 1..TT2_DTW_MAX_FEATS, c0 < 0, a_ld or b_ld < c1, batch < 0, exactly one path
+ * pointer, a path with a workspace below the size query, a null total or length (or a null a / b
+ * with rows to read).  batch, ta or tb = 0 succeeds; with ta or tb = 0 total and length are
+ * written as 0. */
+#define TT2_DTW_MAX_FRAMES 2048
+#define TT2_DTW_MAX_FEATS  32
+typedef struct tt2_dtw_args {
+  const float* a; const float* b;              /* [batch, ta, a_ld], [batch, tb, b_ld] f32, row-major */
+  const int32_t* a_len; const int32_t* b_len;  /* [batch] or NULL (= ta / tb); clamped to [0, ta] / [0, tb] */
+  float* total; int32_t* length;               /* [batch] */
+  int32_t* path_a; int32_t* path_b;            /* [batch, ta + tb - 1], or both NULL: no path wanted */
+  void* workspace; size_t workspace_bytes;
+  int64_t a_ld, b_ld;                          /* floats per row, >= c1 */
+  int32_t batch, ta, tb, c0, c1;               /* features [c0, c1) enter the cost; 1 <= c1 - c0 <= TT2_DTW_MAX_FEATS */
+} tt2_dtw_args;
+size_t tt2_dtw_workspace_size(int batch, int ta, int tb, int want_path);
+int tt2_dtw(const tt2_dtw_args* a, hipStream_t stream);
+
 /* ------------------------------------------------------------------ decode
  * One query row per batch element (the AR decode step):
  * out[b*o_ld + 64h ..] = softmax(scale q k^T) v over keys j < n_b of batch b,

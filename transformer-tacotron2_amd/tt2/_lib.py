@@ -231,6 +231,27 @@ SIGNATURES.update({
 })
 
 
+E_INVALID = -1          # TT2_E_INVALID
+DTW_MAX_FRAMES = 2048  # TT2_DTW_MAX_FRAMES
+DTW_MAX_FEATS = 32      # TT2_DTW_MAX_FEATS
+
+
+class DtwArgs(C.Structure):
+    """tt2_dtw_args: dynamic time warping between two f32 feature sequences per utterance."""
+    _fields_ = [
+        ("a", vp), ("b", vp), ("a_len", vp), ("b_len", vp), ("total", vp), ("length", vp),
+        ("path_a", vp), ("path_b", vp), ("workspace", vp), ("workspace_bytes", sz),
+        ("a_ld", i64), ("b_ld", i64),
+        ("batch", i32), ("ta", i32), ("tb", i32), ("c0", i32), ("c1", i32),
+    ]
+
+
+SIGNATURES.update({
+    "tt2_dtw_workspace_size": ([C.c_int, C.c_int, C.c_int, C.c_int], C.c_size_t),
+    "tt2_dtw": ([C.POINTER(DtwArgs), vp], C.c_int),
+})
+
+
 class ReduceArgs(C.Structure):
     _fields_ = [("src", vp), ("dst", vp), ("ld", i64), ("rows", i32), ("cols", i32), ("beta", f32)]
 

@@ -66,6 +66,15 @@ class MonotonicAlignment(NamedTuple):
     logp: torch.Tensor        # [B] f32: mean over the frames of ln P[n, path[n]]
 
 
+class Evaluation(NamedTuple):
+    """evaluate(): a free-running decode scored against the ground-truth mels (MCD-DTW)."""
+    mcd: torch.Tensor       # [B] f32: mel-cepstral distortion in dB along the DTW path (NaN for an empty decode)
+    length: torch.Tensor    # [B] int32: cells on the DTW path
+    hyp_len: torch.Tensor   # [B]: frames decoded (infer's out_len)
+    ref_len: torch.Tensor   # [B]: the reference lengths as given
+    mel_hyp: torch.Tensor   # [B, T, 80] f32: the decoded mels
+
+
 class _TTSForward(torch.autograd.Function):
     """Teacher-forced forward as one autograd node; backward = the engine's backward from
     the output gradients (it rewrites the flat gradient buffer; a copy is handed to
@@ -421,6 +430,27 @@ class TransformerTTS(nn.Module):
             self._decoders[key] = dec
         dev = self.engine.dev
         return dec.run(text.to(dev), text_len.to(dev), max_len, stop_threshold, use_graph)
+
+    def evaluate(self, text, text_len, mel, mel_len, max_len: int | None = None, stop_threshold: float | None = 0.5,
+                 prenet_dropout: bool = False, n_coef: int = 13, want_path: bool = False) -> Evaluation:
+        """Objective score of a free-running decode: infer(text, ...) and then the mel-cepstral
+        distortion of the decoded mels against `mel` [B, Ty, 80] (natural-log, mel_len [B] frames)
+        along their dynamic-time-warping alignment (tt2.evaluate.mcd_dtw: cepstral columns
+        1..n_coef, dB).  max_len defaults to min(2 Ty, the positional table's rows - 1,
+        TT2_DTW_MAX_FRAMES).  Parameters, BatchNorm statistics, the optimizer and train / eval
+        mode are left as infer() leaves them; the results are fresh tensors, so a captured
+        training step stays valid.  want_path is accepted for symmetry with mcd_dtw; the path
+        itself is returned by mcd_dtw."""
+        from . import _lib
+        from .evaluate import mcd_dtw
+        if max_len is None:
+            max_len = min(2 * mel.shape[1], self.cfg.max_len - 1, _lib.DTW_MAX_FRAMES)
+        mel_hyp, hyp_len = self.infer(text, text_len, max_len, stop_threshold=stop_threshold,
+                                      prenet_dropout=prenet_dropout)
+        dev = self.engine.dev
+        r = mcd_dtw(mel_hyp.float(), hyp_len, mel.to(dev, torch.float32), mel_len.to(dev), n_coef=n_coef,
+                    want_path=want_path)
+        return Evaluation(r.mcd, r.length, hyp_len, mel_len, mel_hyp)
 
     # ------------------------------------------------------------ diagnostics
     def alignments(self, layer: int = -1) -> torch.Tensor:

@@ -554,6 +554,58 @@ def align_monotonic(qs, ks, lses, path, durations, logp, q_ld, k_ld, batch, head
     return path, durations, logp
 
 
+def dtw(a, b, total, length, a_len=None, b_len=None, cols=None, path_a=None, path_b=None, ws=None):
+    """Dynamic time warping (tt2_dtw_args) between a [B, Ta, C] and b [B, Tb, C'] f32 (row views
+    with a contiguous last dim are fine) over the feature columns cols = (c0, c1), default (0, C):
+    total [B] f32 = the accumulated Euclidean frame distance along the best path, length [B] int32
+    = its number of cells, and, when both are given, path_a / path_b [B, Ta + Tb - 1] int32 = its
+    cells in forward order (-1 past length).  a_len / b_len [B] int32 bound the rows used.  On the
+    current stream, no host synchronisation.  Deterministic."""
+    who = "dtw"
+    for name, t in (("a", a), ("b", b)):
+        if t.dtype != torch.float32 or t.dim() != 3 or (t.shape[2] > 1 and t.stride(2) != 1):
+            raise _lib.TT2Error(f"{who}: {name} must be f32 [B, T, C] with a contiguous last dim")
+        if t.shape[0] > 1 and t.shape[1] > 0 and t.stride(0) != t.shape[1] * t.stride(1):
+            raise _lib.TT2Error(f"{who}: {name}'s utterances must follow one another (stride(0) = T * stride(1))")
+    B, ta, tb = a.shape[0], a.shape[1], b.shape[1]
+    if b.shape[0] != B:
+        raise _lib.TT2Error(f"{who}: a and b differ in batch")
+    c0, c1 = (0, a.shape[2]) if cols is None else (int(cols[0]), int(cols[1]))
+    if not (0 <= c0 < c1 <= min(a.shape[2], b.shape[2])) or c1 - c0 > _lib.DTW_MAX_FEATS:
+        raise _lib.TT2Error(f"{who}: cols {(c0, c1)} must lie in both tensors and span 1..{_lib.DTW_MAX_FEATS}")
+    if (path_a is None) != (path_b is None):
+        raise _lib.TT2Error(f"{who}: give both path_a and path_b or neither")
+    _need(f"{who}: total", total, B, torch.float32)
+    _need(f"{who}: length", length, B, torch.int32)
+    tensors = [a, b, total, length]
+    for name, t in (("a_len", a_len), ("b_len", b_len)):
+        if t is not None:
+            _need(f"{who}: {name}", t, B, torch.int32)
+            tensors.append(t)
+    if path_a is not None:
+        for name, t in (("path_a", path_a), ("path_b", path_b)):
+            _need(f"{who}: {name}", t, B * max(0, ta + tb - 1), torch.int32)
+            tensors.append(t)
+    for t in tensors:
+        if t.device != a.device or not t.is_cuda:
+            raise _lib.TT2Error(f"{who}: every tensor must be on a's GPU")
+        if t is not a and t is not b and not t.is_contiguous():
+            raise _lib.TT2Error(f"{who}: outputs and lengths must be contiguous")
+    g = _lib.DtwArgs()
+    g.a, g.b, g.a_len, g.b_len = a.data_ptr(), b.data_ptr(), ptr(a_len), ptr(b_len)
+    g.total, g.length, g.path_a, g.path_b = total.data_ptr(), length.data_ptr(), ptr(path_a), ptr(path_b)
+    g.a_ld, g.b_ld = (a.stride(1) if ta > 1 else max(a.stride(1), a.shape[2])), \
+        (b.stride(1) if tb > 1 else max(b.stride(1), b.shape[2]))
+    g.batch, g.ta, g.tb, g.c0, g.c1 = B, ta, tb, c0, c1
+    L = lib()
+    need = L.tt2_dtw_workspace_size(B, ta, tb, int(path_a is not None))
+    if need:
+        buf = (ws or _WS).get(need)
+        g.workspace, g.workspace_bytes = buf.data_ptr(), buf.numel()
+    check(L.tt2_dtw(C.byref(g), stream_ptr()), "tt2_dtw")
+    return total, length
+
+
 def _drop_into(s, drop: Drop):
     s.drop_seed, s.drop_site, s.drop_thr, s.drop_scale = drop.fields()
 
