@@ -387,6 +387,53 @@ typedef struct tt2_dtw_args {
 size_t tt2_dtw_workspace_size(int batch, int ta, int tb, int want_path);
 int tt2_dtw(const tt2_dtw_args* a, hipStream_t stream);
 
+/* YIN pitch (de Cheveigne & Kawahara 2002, steps 1-5, without the best-local-estimate step) and
+ * RMS energy per frame, on the padded sample buffer tt2_reflect_pad produces.  One wave per frame.
+ * Frame (b, f) is y[j] = x[b * utt_stride + f * hop + j], j < TT2_YIN_FRAME: with hop 256 the
+ * samples of mel frame f.  The integration window is W = TT2_YIN_WINDOW and tau <= TT2_YIN_MAX_LAG,
+ * so W + tau stays inside the frame.  All arithmetic is f32:
+ *   d(tau)    = sum_{j<W} (y[j] - y[j + tau])^2 for tau = 1 .. tau_max, d(0) = 0;
+ *   S(tau)    = sum_{k=1..tau} d(k);
+ *   d'(0)     = 1, d'(tau) = (d(tau) * tau) / S(tau) when S(tau) > 0, else 1: one multiply and one
+ *               correctly rounded divide;
+ *   search    ascending over [tau_min, tau_max]: the first tau with d'(tau) < threshold; while
+ *               tau + 1 <= tau_max and d'(tau + 1) < d'(tau) (strictly), step to tau + 1.  That
+ *               tau is the lag and the frame is voiced.  Without such a tau the frame is unvoiced
+ *               and the lag is the lowest tau that attains the minimum of d' over the range;
+ *   aper      = d'(lag), the same bits;
+ *   f0        = 0 when unvoiced.  Voiced with tau_min < lag < tau_max: with a, b, c = d'(lag - 1),
+ *               d'(lag), d'(lag + 1), off = 0.5 (a - c) / ((a - b) + (c - b)) (the search makes
+ *               a > b and c >= b, so the denominator is positive) and f0 = sr / (lag + off).
+ *               Voiced with the lag at an end of the range: f0 = sr / lag;
+ *   energy    = sqrt((sum_{j<1024} y[j]^2) * 2^-10), an IEEE-rounded square root.
+ * d(tau) is summed over j ascending with one fma per term (the difference is rounded, its square
+ * is not); S(tau) is a running sum over 8 lags plus a scan over groups of 8, and the energy's sum a
+ * tree: fixed orders, not the sequential one.  Where d, S and d * tau are exactly representable
+ * (small integer samples) every output bit is defined by the above.
+ * Frames with f >= clamp(frames[b], 0, t) write f0 = 0, lag = -1, aper = 1, energy = 0, read
+ * nothing, and leave their cmnd row untouched.  A valid frame reads exactly its 1024 samples and
+ * writes cmnd[0 .. tau_max] of its row, nothing after.  A frame with a non-finite sample has
+ * f0 = 0; its other outputs are unspecified.  Results are bit-identical run to run (no
+ * floating-point atomics).
+ * Refused with TT2_E_INVALID before any launch: 1 <= tau_min <= tau_max <= TT2_YIN_MAX_LAG
+ * violated; hop < 1, utt_stride < 0, batch < 0 or t < 0; sr or threshold not finite and positive;
+ * a null f0, lag, aper or energy, or a null x with frames to read; cmnd with cmnd_ld <
+ * tau_max + 1; more than 2^31 - 1 work groups (batch * ceil(t / 4)).  batch = 0 or t = 0 succeeds
+ * without a launch. */
+#define TT2_YIN_FRAME   1024
+#define TT2_YIN_WINDOW  512
+#define TT2_YIN_MAX_LAG 511
+typedef struct tt2_yin_args {
+  const float* x;            /* padded samples; frame (b, f) at x + b*utt_stride + f*hop, 1024 floats */
+  const int32_t* frames;     /* [batch] valid frames, device, or NULL (= t) */
+  float* f0; int32_t* lag; float* aper; float* energy;   /* [batch, t] */
+  float* cmnd;               /* optional [batch, t, cmnd_ld]: d'(0..tau_max) of every valid frame */
+  int64_t utt_stride, cmnd_ld;
+  int32_t batch, t, hop, tau_min, tau_max;
+  float sr, threshold;
+} tt2_yin_args;
+int tt2_yin(const tt2_yin_args* a, hipStream_t stream);
+
 /* ------------------------------------------------------------------ decode
  * One query row per batch element (the AR decode step):
  * out[b*o_ld + 64h ..] = softmax(scale q k^T) v over keys j < n_b of batch b,

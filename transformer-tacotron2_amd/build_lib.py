@@ -23,7 +23,9 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-I" + INCLUDE, 
 # Per-file extras.  Attention keeps MFMA accumulators in arch VGPRs: its softmax reads
 # and rescales them every tile, and the default AGPR placement adds a copy per use.
 EXTRA = {"attention.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"],
-         "attention_mono.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"]}
+         "attention_mono.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"],
+         # YIN's difference loop as plain f32 subtracts and fmas: packed, it measured slower
+         "pitch.hip": ["-fno-slp-vectorize"]}
 
 
 def _headers_mtime() -> float:

@@ -252,6 +252,24 @@ SIGNATURES.update({
 })
 
 
+YIN_FRAME, YIN_WINDOW, YIN_MAX_LAG = 1024, 512, 511   # TT2_YIN_FRAME / _WINDOW / _MAX_LAG
+
+
+class YinArgs(C.Structure):
+    """tt2_yin_args: YIN pitch and RMS energy per frame of a padded sample buffer."""
+    _fields_ = [
+        ("x", vp), ("frames", vp), ("f0", vp), ("lag", vp), ("aper", vp), ("energy", vp), ("cmnd", vp),
+        ("utt_stride", i64), ("cmnd_ld", i64),
+        ("batch", i32), ("t", i32), ("hop", i32), ("tau_min", i32), ("tau_max", i32),
+        ("sr", f32), ("threshold", f32),
+    ]
+
+
+SIGNATURES.update({
+    "tt2_yin": ([C.POINTER(YinArgs), vp], C.c_int),
+})
+
+
 class ReduceArgs(C.Structure):
     _fields_ = [("src", vp), ("dst", vp), ("ld", i64), ("rows", i32), ("cols", i32), ("beta", f32)]
 

@@ -7,6 +7,9 @@
 * ``GriffinLim``: synthesised log-mels -> waveform (mel -> linear magnitude by the
   filterbank's pseudo-inverse, then Griffin-Lim with the least-squares iSTFT): the
   vocoder hand-off for listening tests.
+* ``PitchExtractor``: waveform batch -> YIN F0, voicing, aperiodicity and RMS energy per
+  frame of the same grid (tt2_yin on the reflect-padded buffer), and ``phoneme_average``
+  for the phoneme-level pitch and energy of a duration-based student.
 
 Every transform runs on the GPU through libtt2: the window-folded DFT basis, its
 inverse and the mel filterbank are f32 ``tt2_gemm`` operands (constant tables built
@@ -18,6 +21,7 @@ is a multiple of the hop (see include/tt2_capi.h).
 from __future__ import annotations
 
 import math
+from typing import NamedTuple
 
 import torch
 
@@ -186,3 +190,76 @@ class GriffinLim:
             mx.stft(y, lens, P)
             est = P.spec
         return y, lens
+
+
+class Pitch(NamedTuple):
+    """PitchExtractor(): per-frame pitch features on MelExtractor's frame grid."""
+    f0: torch.Tensor             # [B, T] f32, Hz; 0 where unvoiced or past the utterance
+    voiced: torch.Tensor         # [B, T] bool
+    aperiodicity: torch.Tensor   # [B, T] f32: d'(lag) of YIN, 1 past the utterance
+    energy: torch.Tensor         # [B, T] f32: RMS of the frame's 1024 samples, 0 past the utterance
+    frames: torch.Tensor         # [B] int32
+
+
+class PitchExtractor:
+    """YIN pitch (tt2_yin; include/tt2_capi.h has the definition) and RMS energy of every mel frame.
+    Lags run from ceil(sr / fmax) to min(511, floor(sr / fmin)): at 22.05 kHz a pitch below 43.2 Hz
+    is out of reach of the 1024-sample frame."""
+
+    def __init__(self, extractor: MelExtractor | None = None, fmin: float = 65.0, fmax: float = 600.0,
+                 threshold: float = 0.1):
+        if not (0 < fmin <= fmax) or not threshold > 0:
+            raise ValueError("PitchExtractor: 0 < fmin <= fmax and threshold > 0")
+        self.mx = extractor or MelExtractor()
+        self.fmin, self.fmax, self.threshold = float(fmin), float(fmax), float(threshold)
+        self.tau_min = max(1, math.ceil(SR / fmax))
+        self.tau_max = min(N_FFT // 2 - 1, math.floor(SR / fmin))
+        if self.tau_min > self.tau_max:
+            raise ValueError(f"PitchExtractor: no lag between {fmin} and {fmax} Hz fits the frame")
+
+    def params(self) -> dict:
+        return {"sr": SR, "hop": HOP, "frame": N_FFT, "fmin": self.fmin, "fmax": self.fmax,
+                "threshold": self.threshold, "tau_min": self.tau_min, "tau_max": self.tau_max}
+
+    def __call__(self, audio: torch.Tensor, lens: torch.Tensor | None = None) -> Pitch:
+        """audio [B, L] f32, lens [B] samples (optional, each > 512) -> Pitch with [B, T] tensors,
+        T = 1 + L // 256 and frames = 1 + lens // 256: MelExtractor's grid.  One tt2_reflect_pad
+        into the extractor's plan buffer and one tt2_yin launch on the current stream; no host
+        synchronisation; the results are fresh tensors."""
+        B, Lx = audio.shape
+        dev = self.mx.dev
+        audio = audio.to(dev, torch.float32).contiguous()
+        P = self.mx.plan(B, Lx)
+        lens32 = lens.to(dev, torch.int32) if lens is not None else None
+        check(lib().tt2_reflect_pad(audio.data_ptr(), audio.stride(0), ptr(lens32), P.B, P.L, P.padded.data_ptr(),
+                                    P.Lp, N_FFT // 2, stream_ptr()), "tt2_reflect_pad")
+        frames = (1 + lens32 // HOP) if lens32 is not None else torch.full((B,), P.T, dtype=torch.int32, device=dev)
+        f0 = torch.empty(B, P.T, dtype=torch.float32, device=dev)
+        lag = torch.empty(B, P.T, dtype=torch.int32, device=dev)
+        aper, energy = torch.empty_like(f0), torch.empty_like(f0)
+        ops.yin(P.padded, P.Lp, f0, lag, aper, energy, HOP, self.tau_min, self.tau_max, SR, self.threshold,
+                frames=frames)
+        return Pitch(f0, f0 > 0, aper, energy, frames)
+
+
+def phoneme_average(values: torch.Tensor, durations: torch.Tensor, mask: torch.Tensor | None = None) -> torch.Tensor:
+    """Mean of values [B, T] over each phoneme's run of frames (phoneme p of utterance b owns the
+    durations[b, p] frames after those of the phonemes before it), over the frames where mask
+    [B, T] is true (default: all); 0 where a phoneme has no such frame.  Frames past the sum of
+    the durations belong to no phoneme.  [B, Tx] in values' dtype, on values' device; cumulative
+    sums in float64, no loop over frames (FastSpeech 2's phoneme-level pitch and energy)."""
+    if values.dim() != 2 or durations.dim() != 2 or values.shape[0] != durations.shape[0]:
+        raise ValueError("phoneme_average: values [B, T] and durations [B, Tx]")
+    B, T = values.shape
+    dev = values.device
+    m = torch.ones(B, T, dtype=torch.float64, device=dev) if mask is None else mask.to(dev, torch.float64)
+    v = torch.where(m > 0, values.to(torch.float64), torch.zeros((), dtype=torch.float64, device=dev))
+    zero = torch.zeros(B, 1, dtype=torch.float64, device=dev)
+    cs = torch.cat([zero, v.cumsum(1)], 1)          # [B, T + 1]: sums of the frames before each index
+    cn = torch.cat([zero, m.cumsum(1)], 1)
+    end = durations.to(dev, torch.long).clamp_min(0).cumsum(1).clamp(max=T)
+    start = torch.cat([torch.zeros(B, 1, dtype=torch.long, device=dev), end[:, :-1]], 1)
+    tot = cs.gather(1, end) - cs.gather(1, start)
+    cnt = cn.gather(1, end) - cn.gather(1, start)
+    out = torch.where(cnt > 0, tot / cnt.clamp_min(1.0), torch.zeros_like(tot))
+    return out.to(values.dtype)

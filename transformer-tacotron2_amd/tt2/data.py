@@ -212,3 +212,60 @@ def extract_durations(model, batches, out_dir: str, head="best", method="argmax"
     with open(os.path.join(out_dir, "durations.json"), "w") as f:
         json.dump(manifest, f, indent=1, sort_keys=True)
     return manifest
+
+
+def extract_pitch(batches, out_dir: str, extractor, durations_dir: str | None = None):
+    """Frame-level pitch and energy of every utterance in `batches`, an iterable of
+    (ids, audio [B, L], lens [B] samples), through extractor(audio, lens) -> a tt2.audio.Pitch
+    (f0, voiced, aperiodicity, energy, frames): a tt2.audio.PitchExtractor, or a stub in tests.
+    Writes per utterance out_dir/<id>.f0.npy and <id>.energy.npy (f32 [frames]; f0 is 0 where
+    unvoiced).  Where durations_dir holds <id>.npy (extract_durations' output), also
+    <id>.f0_ph.npy and <id>.energy_ph.npy (f32 [phonemes]): tt2.audio.phoneme_average over each
+    phoneme's frames, the pitch over its voiced frames only (0 for a phoneme without one).  An
+    utterance whose durations do not sum to its frame count is refused with a ValueError that
+    names it.  Writes out_dir/pitch.json: {"extractor": its params(), "utterances": {id:
+    {"frames", "voiced"}} with voiced the share of voiced frames, "log_f0": {"mean", "std",
+    "frames"} over all voiced frames (natural log), "energy": {"mean", "std", "frames"} over
+    all frames}; the standard deviations are the population ones.  Returns the manifest."""
+    from .audio import phoneme_average
+    os.makedirs(out_dir, exist_ok=True)
+    params = extractor.params() if hasattr(extractor, "params") else {}
+    manifest = {"extractor": params, "utterances": {}}
+    acc = {"log_f0": [0, 0.0, 0.0], "energy": [0, 0.0, 0.0]}   # count, sum, sum of squares (float64 on the host)
+
+    def add(key, x):
+        x = x.astype(np.float64)
+        acc[key][0] += x.size
+        acc[key][1] += float(x.sum())
+        acc[key][2] += float((x * x).sum())
+
+    for ids, audio, lens in batches:
+        p = extractor(audio, lens)
+        f0, energy = p.f0.detach().float().cpu(), p.energy.detach().float().cpu()
+        voiced = p.voiced.detach().cpu()
+        frames = [int(n) for n in torch.as_tensor(p.frames).cpu()]
+        for b, uid in enumerate(ids):
+            n = min(frames[b], f0.shape[1])
+            f, e, v = f0[b, :n].numpy(), energy[b, :n].numpy(), voiced[b, :n].numpy().astype(bool)
+            np.save(os.path.join(out_dir, f"{uid}.f0.npy"), np.ascontiguousarray(f, dtype=np.float32))
+            np.save(os.path.join(out_dir, f"{uid}.energy.npy"), np.ascontiguousarray(e, dtype=np.float32))
+            manifest["utterances"][str(uid)] = {"frames": n, "voiced": float(v.mean()) if n else 0.0}
+            add("log_f0", np.log(f[v].astype(np.float64)))
+            add("energy", e)
+            dpath = os.path.join(durations_dir, f"{uid}.npy") if durations_dir else None
+            if dpath and os.path.exists(dpath):
+                d = np.load(dpath)
+                if int(d.sum()) != n:
+                    raise ValueError(f"extract_pitch: durations of {uid} sum to {int(d.sum())} frames, "
+                                     f"its audio has {n}")
+                dt_ = torch.from_numpy(d.astype(np.int64))[None]
+                f_ph = phoneme_average(f0[b:b + 1, :n], dt_, voiced[b:b + 1, :n])[0].numpy()
+                e_ph = phoneme_average(energy[b:b + 1, :n], dt_)[0].numpy()
+                np.save(os.path.join(out_dir, f"{uid}.f0_ph.npy"), np.ascontiguousarray(f_ph, dtype=np.float32))
+                np.save(os.path.join(out_dir, f"{uid}.energy_ph.npy"), np.ascontiguousarray(e_ph, dtype=np.float32))
+    for key, (cnt, s, s2) in acc.items():
+        mean = s / cnt if cnt else 0.0
+        manifest[key] = {"mean": mean, "std": max(s2 / cnt - mean * mean, 0.0) ** 0.5 if cnt else 0.0, "frames": cnt}
+    with open(os.path.join(out_dir, "pitch.json"), "w") as f:
+        json.dump(manifest, f, indent=1, sort_keys=True)
+    return manifest

@@ -7,6 +7,9 @@ along the best monotone alignment of the two sequences:
     dtw      tt2_dtw over the cepstral columns 1..n_coef (column 0, the frame energy, is left out)
     mcd      (10 / ln 10) * sqrt(2) * total / length, in dB
 
+and, for waveforms, by pitch along the same path (f0_metrics, f0_dtw): log-F0 RMSE in cents, gross
+pitch error and voicing-decision error of the YIN tracks of tt2.audio.PitchExtractor.
+
 Everything runs on the current stream without host synchronisation; results are fresh tensors
 outside any arena, and the move-code scratch is this module's own, so a captured training step
 stays valid.
@@ -42,6 +45,14 @@ class MCD(NamedTuple):
     length: torch.Tensor   # [B] int32
     path_hyp: torch.Tensor | None
     path_ref: torch.Tensor | None
+
+
+class F0Score(NamedTuple):
+    """f0_metrics(): pitch agreement of two F0 tracks along a DTW path."""
+    rmse_cents: torch.Tensor     # [B] f32: RMS of 1200 log2(f_hyp / f_ref) over the doubly voiced cells (NaN: none)
+    vuv_error: torch.Tensor      # [B] f32: share of the path's cells whose voicing differs (NaN: empty path)
+    gpe: torch.Tensor            # [B] f32: share of the doubly voiced cells with |f_hyp / f_ref - 1| > 0.2 (NaN: none)
+    voiced_pairs: torch.Tensor   # [B] int32: cells voiced on both sides
 
 
 def dct_basis(n_mels: int = 80, n_coef: int = 13) -> torch.Tensor:
@@ -103,3 +114,41 @@ def mcd_dtw(mel_hyp, hyp_len, mel_ref, ref_len, n_coef: int = 13, want_path: boo
     mcd = MCD_SCALE * r.total / r.length.float()
     mcd = torch.where(r.length > 0, mcd, torch.full_like(mcd, float("nan")))
     return MCD(mcd, r.total, r.length, r.path_a, r.path_b)
+
+
+def f0_metrics(f0_hyp, f0_ref, path_hyp, path_ref, length) -> F0Score:
+    """Pitch agreement of two F0 tracks [B, Th] and [B, Tr] (Hz, 0 = unvoiced) over the first
+    length[b] cells of a DTW path (path_hyp / path_ref [B, P] frame indices, as mcd_dtw returns
+    them with want_path=True).  A cell is voiced on a side when that side's f0 there is > 0.
+    Sums in float64 on the tracks' device; no host synchronisation."""
+    dev = f0_hyp.device
+    P = path_hyp.shape[1]
+    length = length.to(dev)
+    live = (torch.arange(P, device=dev)[None, :] < length[:, None]) & (path_hyp >= 0) & (path_ref >= 0)
+    fh = f0_hyp.to(torch.float64).gather(1, path_hyp.clamp_min(0).long())
+    fr = f0_ref.to(torch.float64).gather(1, path_ref.clamp_min(0).long())
+    vh, vr = (fh > 0) & live, (fr > 0) & live
+    both = vh & vr
+    one = torch.ones((), dtype=torch.float64, device=dev)
+    ratio = torch.where(both, fh / torch.where(both, fr, one), one)
+    cents = 1200.0 * torch.log2(ratio)
+    n = both.sum(1).to(torch.float64)
+    cells = live.sum(1).to(torch.float64)
+    rmse = torch.sqrt((cents * cents).sum(1) / n)                       # 0 / 0 = NaN where nothing is voiced twice
+    gpe = (((ratio - 1.0).abs() > 0.2) & both).sum(1).to(torch.float64) / n
+    vuv = (vh != vr).sum(1).to(torch.float64) / cells
+    return F0Score(rmse.float(), vuv.float(), gpe.float(), both.sum(1).to(torch.int32))
+
+
+def f0_dtw(wav_hyp, hyp_len, wav_ref, ref_len, n_coef: int = 13, pitch=None):
+    """F0 agreement of two waveform batches [B, Lh] and [B, Lr] (hyp_len / ref_len [B] samples or
+    None) along the DTW alignment of their mel cepstra: mels of both sides, mcd_dtw with the path,
+    YIN pitch of both sides (pitch: a tt2.audio.PitchExtractor, default parameters otherwise),
+    f0_metrics.  Returns (F0Score, MCD).  At most 2048 frames per side (tt2_dtw)."""
+    from .audio import PitchExtractor
+    px = pitch or PitchExtractor()
+    mel_h, fr_h = px.mx(wav_hyp, hyp_len)
+    mel_r, fr_r = px.mx(wav_ref, ref_len)
+    m = mcd_dtw(mel_h, fr_h, mel_r, fr_r, n_coef=n_coef, want_path=True)
+    ph, pr = px(wav_hyp, hyp_len), px(wav_ref, ref_len)
+    return f0_metrics(ph.f0, pr.f0, m.path_hyp, m.path_ref, m.length), m

@@ -606,6 +606,52 @@ def dtw(a, b, total, length, a_len=None, b_len=None, cols=None, path_a=None, pat
     return total, length
 
 
+def yin(x, utt_stride, f0, lag, aper, energy, hop, tau_min, tau_max, sr, threshold, frames=None, cmnd=None):
+    """YIN pitch and RMS energy (tt2_yin_args) of the frames of x, a contiguous f32 buffer of padded
+    samples: frame (b, f) is the 1024 samples from b * utt_stride + f * hop.  f0 / aper / energy
+    [B, T] f32 and lag [B, T] int32 are written; frames [B] int32 bounds the valid frames of each
+    utterance (the others get f0 0, lag -1, aper 1, energy 0); cmnd [B, T, ld] f32, when given,
+    receives d'(0 .. tau_max) of every valid frame.  On the current stream, no host
+    synchronisation.  Deterministic."""
+    who = "yin"
+    if f0.dim() != 2:
+        raise _lib.TT2Error(f"{who}: f0 must be [B, T]")
+    B, T = f0.shape
+    if x.dtype != torch.float32 or not x.is_contiguous():
+        raise _lib.TT2Error(f"{who}: x must be a contiguous f32 buffer")
+    utt_stride, hop = int(utt_stride), int(hop)
+    if B and T and (utt_stride < 0 or hop < 1 or (B - 1) * utt_stride + (T - 1) * hop + _lib.YIN_FRAME > x.numel()):
+        raise _lib.TT2Error(f"{who}: x holds {x.numel()} samples, fewer than the last frame needs")
+    tensors = [x]
+    for name, t, dtype in (("f0", f0, torch.float32), ("lag", lag, torch.int32), ("aper", aper, torch.float32),
+                           ("energy", energy, torch.float32)):
+        _need(f"{who}: {name}", t, B * T, dtype)
+        tensors.append(t)
+    if frames is not None:
+        _need(f"{who}: frames", frames, B, torch.int32)
+        tensors.append(frames)
+    ld = 0
+    if cmnd is not None:
+        if cmnd.dim() != 3 or cmnd.shape[0] != B or cmnd.shape[1] != T:
+            raise _lib.TT2Error(f"{who}: cmnd must be [B, T, ld]")
+        ld = cmnd.shape[2]
+        _need(f"{who}: cmnd", cmnd, B * T * ld, torch.float32)
+        tensors.append(cmnd)
+    for t in tensors:
+        if t.device != f0.device or not t.is_cuda:
+            raise _lib.TT2Error(f"{who}: every tensor must be on f0's GPU")
+        if not t.is_contiguous():
+            raise _lib.TT2Error(f"{who}: every tensor must be contiguous")
+    g = _lib.YinArgs()
+    g.x, g.frames, g.cmnd = x.data_ptr(), ptr(frames), ptr(cmnd)
+    g.f0, g.lag, g.aper, g.energy = f0.data_ptr(), lag.data_ptr(), aper.data_ptr(), energy.data_ptr()
+    g.utt_stride, g.cmnd_ld = utt_stride, ld
+    g.batch, g.t, g.hop, g.tau_min, g.tau_max = B, T, hop, int(tau_min), int(tau_max)
+    g.sr, g.threshold = float(sr), float(threshold)
+    check(lib().tt2_yin(C.byref(g), stream_ptr()), "tt2_yin")
+    return f0, lag, aper, energy
+
+
 def _drop_into(s, drop: Drop):
     s.drop_seed, s.drop_site, s.drop_thr, s.drop_scale = drop.fields()
 
