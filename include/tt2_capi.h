@@ -434,6 +434,57 @@ typedef struct tt2_yin_args {
 } tt2_yin_args;
 int tt2_yin(const tt2_yin_args* a, hipStream_t stream);
 
+/* Viterbi pitch tracking over the d' that tt2_yin writes to `cmnd`: one path per utterance through
+ * the lags and one unvoiced state, instead of tt2_yin's decision per frame.  One work group per
+ * utterance.  For utterance b, N = clamp(frames[b], 0, t) (frames NULL: N = t).  The states are the
+ * lags tau in [tau_min, tau_max] plus one unvoiced state; c(f, tau) = cmnd[(b * t + f) * cmnd_ld + tau];
+ * p = the `pos` table (f32, [tau_max + 1], device); J, W, C = jump, switch_cost, unvoiced.  All
+ * arithmetic is f32:
+ *   V[0][tau] = c(0, tau)                    U[0] = C
+ *   A[f][tau] = min over tau' of ( V[f-1][tau'] + J * |p[tau] - p[tau']| ); the lowest tau' wins a tie
+ *   V[f][tau] = c(f, tau) + ( U[f-1] + W if that is strictly less than A[f][tau], else A[f][tau] )
+ *   m[f]      = min over tau' of V[f-1][tau'] (the lowest tau' on a tie)
+ *   U[f]      = C + ( m[f] + W if that is strictly less than U[f-1], else U[f-1] )
+ *   end       unvoiced if U[N-1] is strictly less than min over tau of V[N-1][tau], else the lowest
+ *             tau of that minimum
+ *   cost[b]   = the end state's value; 0 when N = 0.
+ * |p[tau] - p[tau']| is one subtraction; J times it plus V is one fma here (two rounded operations
+ * give the same bits wherever the product is exact).  A minimum of f32 values does not depend on
+ * the order in which it is taken, and the kernel splits it across waves.  The path follows the
+ * recorded decisions back from the end state:
+ *   lag[b][f]  the lag of a voiced frame, 0 for an unvoiced frame f < N, -1 for f >= N;
+ *   f0[b][f]   0 when unvoiced or f >= N.  Voiced with lag tau and a, b, c = c(f, tau - 1), c(f, tau),
+ *              c(f, tau + 1): if tau_min < tau < tau_max, a > b and c >= b, then f0 = sr / (tau + off),
+ *              off = 0.5 (a - c) / ((a - b) + (c - b)), tt2_yin's operations with IEEE divides;
+ *              otherwise f0 = sr / tau.  (The tracked lag need not be a local minimum of d'.)
+ * Only columns [tau_min, tau_max] of rows f < N of cmnd are read; every element of f0 and lag with
+ * f < t is written.  A non-finite cmnd value in a valid frame leaves that utterance's outputs
+ * unspecified, but every lag written is -1, 0 or inside the range, nothing is read or written out
+ * of bounds and the other utterances are unaffected.  Results are bit-identical run to run (no
+ * floating-point atomics, no hand-off between work groups).
+ * `workspace` (4-B aligned) of tt2_pitch_track_workspace_size bytes holds the value history the
+ * backtrack reads: per utterance [t][tau_max - tau_min + 2] f32, V of the lags then U.  The size is
+ * 0 when batch or t is 0 (or the lag range is malformed).
+ * Refused with TT2_E_INVALID before any launch: t > TT2_PITCH_TRACK_MAX_FRAMES; 1 <= tau_min <=
+ * tau_max <= TT2_YIN_MAX_LAG violated; batch < 0 or t < 0; cmnd_ld < tau_max + 1; sr not finite and
+ * positive; jump, switch_cost or unvoiced not finite or negative; a null f0, lag, cost or pos; a
+ * null cmnd with frames to read; a workspace below the size query.  batch = 0 or t = 0 succeeds
+ * without a kernel launch; with t = 0 and batch > 0 cost is set to 0 (a memset on the stream). */
+#define TT2_PITCH_TRACK_MAX_FRAMES 4096
+typedef struct tt2_pitch_track_args {
+  const float* cmnd;         /* [batch, t, cmnd_ld] f32: d' as tt2_yin writes it */
+  const int32_t* frames;     /* [batch] valid frames, device, or NULL (= t) */
+  const float* pos;          /* [tau_max + 1] f32, device: the position of each lag on the jump axis */
+  float* f0; int32_t* lag;   /* [batch, t] */
+  float* cost;               /* [batch] */
+  void* workspace; size_t workspace_bytes;
+  int64_t cmnd_ld;           /* floats per row, >= tau_max + 1 */
+  int32_t batch, t, tau_min, tau_max;
+  float sr, jump, switch_cost, unvoiced;   /* `switch` of the definition: a keyword in C */
+} tt2_pitch_track_args;
+size_t tt2_pitch_track_workspace_size(int batch, int t, int tau_min, int tau_max);
+int tt2_pitch_track(const tt2_pitch_track_args* a, hipStream_t stream);
+
 /* ------------------------------------------------------------------ decode
  * One query row per batch element (the AR decode step):
  * out[b*o_ld + 64h ..] = softmax(scale q k^T) v over keys j < n_b of batch b,

@@ -7,8 +7,14 @@ A thin command line over tt2.data.extract_pitch: YIN pitch and RMS energy on the
 <id>.f0_ph.npy and <id>.energy_ph.npy: with the durations, the targets of a FastSpeech 2 style
 student.
 
+With --track viterbi the F0 and the voicing come from tt2.audio.PitchTracker instead: one path per
+utterance through the lags and an unvoiced state over the same d' (one tt2_pitch_track launch
+more per batch), which removes the octave-up frames and mid-vowel dropouts of the per-frame
+decision.  --jump, --switch and --unvoiced are its three costs; pitch.json records them.
+
     python tools/extract_pitch.py --data /data/LJSpeech-1.1 --out pitch/ [--durations durations/] \
-        [--batch 16] [--fmin 65] [--fmax 600] [--threshold 0.1] [--limit N]
+        [--batch 16] [--fmin 65] [--fmax 600] [--threshold 0.1] [--limit N] \
+        [--track viterbi [--jump 1.0] [--switch 0.1] [--unvoiced 0.2]]
 """
 import argparse
 import json
@@ -29,18 +35,32 @@ def parse_args(argv=None):
     ap.add_argument("--fmax", type=float, default=600.0)
     ap.add_argument("--threshold", type=float, default=0.1)
     ap.add_argument("--limit", type=int, default=0, help="only the first N utterances (0: all)")
+    ap.add_argument("--track", choices=["none", "viterbi"], default="none",
+                    help="viterbi: F0 and voicing from tt2.audio.PitchTracker (default: the per-frame decision)")
+    ap.add_argument("--jump", type=float, default=1.0, help="--track viterbi: cost of moving one octave")
+    ap.add_argument("--switch", type=float, default=0.1, help="--track viterbi: cost of a change of voicing")
+    ap.add_argument("--unvoiced", type=float, default=0.2, help="--track viterbi: cost of an unvoiced frame")
     return ap.parse_args(argv)
+
+
+def make_extractor(a):
+    """The extractor the arguments ask for: a PitchExtractor, inside a PitchTracker with --track viterbi."""
+    from tt2 import audio
+
+    px = audio.PitchExtractor(fmin=a.fmin, fmax=a.fmax, threshold=a.threshold)
+    if a.track == "viterbi":
+        px = audio.PitchTracker(px, jump=a.jump, switch=a.switch, unvoiced=a.unvoiced)
+    return px
 
 
 def main(argv=None):
     a = parse_args(argv)
     import torch
 
-    from tt2.audio import PitchExtractor
     from tt2.data import LJSpeech, extract_pitch
 
     ds = LJSpeech(a.data)
-    px = PitchExtractor(fmin=a.fmin, fmax=a.fmax, threshold=a.threshold)
+    px = make_extractor(a)
     n = min(len(ds), a.limit) if a.limit else len(ds)
 
     def batches():   # one batch resident at a time, in corpus order

@@ -270,6 +270,25 @@ SIGNATURES.update({
 })
 
 
+PITCH_TRACK_MAX_FRAMES = 4096   # TT2_PITCH_TRACK_MAX_FRAMES
+
+
+class PitchTrackArgs(C.Structure):
+    """tt2_pitch_track_args: Viterbi pitch tracking over the d' of tt2_yin."""
+    _fields_ = [
+        ("cmnd", vp), ("frames", vp), ("pos", vp), ("f0", vp), ("lag", vp), ("cost", vp),
+        ("workspace", vp), ("workspace_bytes", sz), ("cmnd_ld", i64),
+        ("batch", i32), ("t", i32), ("tau_min", i32), ("tau_max", i32),
+        ("sr", f32), ("jump", f32), ("switch_cost", f32), ("unvoiced", f32),
+    ]
+
+
+SIGNATURES.update({
+    "tt2_pitch_track_workspace_size": ([C.c_int, C.c_int, C.c_int, C.c_int], C.c_size_t),
+    "tt2_pitch_track": ([C.POINTER(PitchTrackArgs), vp], C.c_int),
+})
+
+
 class ReduceArgs(C.Structure):
     _fields_ = [("src", vp), ("dst", vp), ("ld", i64), ("rows", i32), ("cols", i32), ("beta", f32)]
 

@@ -10,6 +10,8 @@
 * ``PitchExtractor``: waveform batch -> YIN F0, voicing, aperiodicity and RMS energy per
   frame of the same grid (tt2_yin on the reflect-padded buffer), and ``phoneme_average``
   for the phoneme-level pitch and energy of a duration-based student.
+* ``PitchTracker``: the same, with F0 and voicing from one Viterbi path per utterance through
+  the lags and an unvoiced state over YIN's d' (tt2_pitch_track) instead of a decision per frame.
 
 Every transform runs on the GPU through libtt2: the window-folded DFT basis, its
 inverse and the mel filterbank are f32 ``tt2_gemm`` operands (constant tables built
@@ -226,6 +228,12 @@ class PitchExtractor:
         T = 1 + L // 256 and frames = 1 + lens // 256: MelExtractor's grid.  One tt2_reflect_pad
         into the extractor's plan buffer and one tt2_yin launch on the current stream; no host
         synchronisation; the results are fresh tensors."""
+        f0, _, aper, energy, frames, _ = self._yin(audio, lens, False)
+        return Pitch(f0, f0 > 0, aper, energy, frames)
+
+    def _yin(self, audio, lens, want_cmnd: bool):
+        """The pad and the tt2_yin launch -> (f0, lag, aper, energy, frames, cmnd or None), fresh
+        tensors; cmnd [B, T, tau_max + 1] is d'(0 .. tau_max) of every valid frame (PitchTracker)."""
         B, Lx = audio.shape
         dev = self.mx.dev
         audio = audio.to(dev, torch.float32).contiguous()
@@ -237,9 +245,67 @@ class PitchExtractor:
         f0 = torch.empty(B, P.T, dtype=torch.float32, device=dev)
         lag = torch.empty(B, P.T, dtype=torch.int32, device=dev)
         aper, energy = torch.empty_like(f0), torch.empty_like(f0)
+        cmnd = torch.empty(B, P.T, self.tau_max + 1, dtype=torch.float32, device=dev) if want_cmnd else None
         ops.yin(P.padded, P.Lp, f0, lag, aper, energy, HOP, self.tau_min, self.tau_max, SR, self.threshold,
-                frames=frames)
-        return Pitch(f0, f0 > 0, aper, energy, frames)
+                frames=frames, cmnd=cmnd)
+        return f0, lag, aper, energy, frames, cmnd
+
+
+class PitchTrack(NamedTuple):
+    """PitchTracker.track(): the Pitch plus the tracked lags and the cost of each utterance's path."""
+    pitch: Pitch
+    lag: torch.Tensor            # [B, T] int32: the lag of a voiced frame, 0 unvoiced, -1 past the utterance
+    cost: torch.Tensor           # [B] f32
+
+
+class PitchTracker:
+    """Viterbi pitch tracking (tt2_pitch_track; include/tt2_capi.h has the definition) over the d'
+    of a PitchExtractor's tt2_yin launch: one path per utterance through the extractor's lags and
+    one unvoiced state instead of a decision per frame.  A move between two lags costs `jump` per
+    octave (pos = log2 of the lag), a change of voicing costs `switch`, and an unvoiced frame costs
+    `unvoiced` where a voiced one costs its d'.  The three defaults were chosen on synthetic signals
+    only.  A drop-in for PitchExtractor wherever a Pitch is wanted (data.extract_pitch,
+    evaluate.f0_dtw)."""
+
+    def __init__(self, extractor: PitchExtractor | None = None, jump: float = 1.0, switch: float = 0.1,
+                 unvoiced: float = 0.2):
+        for name, v in (("jump", jump), ("switch", switch), ("unvoiced", unvoiced)):
+            if not (math.isfinite(v) and v >= 0):
+                raise ValueError(f"PitchTracker: {name} must be finite and not negative")
+        self.px = extractor or PitchExtractor()
+        self.jump, self.switch, self.unvoiced = float(jump), float(switch), float(unvoiced)
+        self._pos = None
+
+    mx = property(lambda self: self.px.mx)
+    tau_min = property(lambda self: self.px.tau_min)
+    tau_max = property(lambda self: self.px.tau_max)
+
+    def params(self) -> dict:
+        return {**self.px.params(), "track": "viterbi", "jump": self.jump, "switch": self.switch,
+                "unvoiced": self.unvoiced}
+
+    def pos(self) -> torch.Tensor:
+        """log2(tau) for tau = 0 .. tau_max (entry 0 is 0 and never read): float64 on the host,
+        rounded to f32."""
+        if self._pos is None:
+            tau = torch.arange(self.tau_max + 1, dtype=torch.float64).clamp_min(1.0)
+            self._pos = torch.log2(tau).float().to(self.mx.dev)
+        return self._pos
+
+    def track(self, audio: torch.Tensor, lens: torch.Tensor | None = None) -> PitchTrack:
+        """audio [B, L] f32, lens [B] samples (optional, each > 512), as PitchExtractor takes them.
+        One pad, one tt2_yin launch that also writes d' into a fresh tensor, one tt2_pitch_track
+        launch; no host synchronisation.  f0 and voiced are the tracker's; aperiodicity, energy and
+        frames are tt2_yin's, the bits PitchExtractor returns."""
+        _, lag, aper, energy, frames, cmnd = self.px._yin(audio, lens, True)
+        f0 = torch.empty_like(aper)
+        cost = torch.empty(aper.shape[0], dtype=torch.float32, device=aper.device)
+        ops.pitch_track(cmnd, frames, f0, lag, cost, self.tau_min, self.tau_max, SR, self.pos(), self.jump,
+                        self.switch, self.unvoiced)
+        return PitchTrack(Pitch(f0, lag > 0, aper, energy, frames), lag, cost)
+
+    def __call__(self, audio: torch.Tensor, lens: torch.Tensor | None = None) -> Pitch:
+        return self.track(audio, lens).pitch
 
 
 def phoneme_average(values: torch.Tensor, durations: torch.Tensor, mask: torch.Tensor | None = None) -> torch.Tensor:

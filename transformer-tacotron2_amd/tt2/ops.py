@@ -652,6 +652,55 @@ def yin(x, utt_stride, f0, lag, aper, energy, hop, tau_min, tau_max, sr, thresho
     return f0, lag, aper, energy
 
 
+def pitch_track(cmnd, frames, f0, lag, cost, tau_min, tau_max, sr, pos, jump, switch, unvoiced, ws=None):
+    """Viterbi pitch tracking (tt2_pitch_track_args) over cmnd [B, T, ld] f32, the d' that yin
+    writes (a row view with a contiguous last dim is fine): f0 [B, T] f32, lag [B, T] int32 (0
+    unvoiced, -1 past the utterance) and cost [B] f32 are written.  frames [B] int32 (or None: T)
+    bounds the valid frames of each utterance; pos [>= tau_max + 1] f32 places each lag on the axis
+    that `jump` prices; `switch` is paid on a change of voicing and `unvoiced` per unvoiced frame.
+    On the current stream, no host synchronisation.  Deterministic."""
+    who = "pitch_track"
+    if cmnd.dtype != torch.float32 or cmnd.dim() != 3 or (cmnd.shape[2] > 1 and cmnd.stride(2) != 1):
+        raise _lib.TT2Error(f"{who}: cmnd must be f32 [B, T, ld] with a contiguous last dim")
+    B, T, width = cmnd.shape
+    tau_min, tau_max = int(tau_min), int(tau_max)
+    if not (1 <= tau_min <= tau_max <= _lib.YIN_MAX_LAG):
+        raise _lib.TT2Error(f"{who}: lags must satisfy 1 <= tau_min <= tau_max <= {_lib.YIN_MAX_LAG}")
+    if T > _lib.PITCH_TRACK_MAX_FRAMES:
+        raise _lib.TT2Error(f"{who}: {T} frames exceed {_lib.PITCH_TRACK_MAX_FRAMES}")
+    if width < tau_max + 1:
+        raise _lib.TT2Error(f"{who}: cmnd rows hold {width} values, fewer than tau_max + 1")
+    ld = cmnd.stride(1) if T > 1 else max(cmnd.stride(1), width)
+    if ld < width or (B > 1 and T > 0 and cmnd.stride(0) != T * ld):
+        raise _lib.TT2Error(f"{who}: cmnd's rows must follow one another (stride(0) = T * stride(1) >= ld)")
+    _need(f"{who}: f0", f0, B * T, torch.float32)
+    _need(f"{who}: lag", lag, B * T, torch.int32)
+    _need(f"{who}: cost", cost, B, torch.float32)
+    _need(f"{who}: pos", pos, tau_max + 1, torch.float32)
+    tensors = [cmnd, f0, lag, cost, pos]
+    if frames is not None:
+        _need(f"{who}: frames", frames, B, torch.int32)
+        tensors.append(frames)
+    for t in tensors:
+        if t.device != cmnd.device or not t.is_cuda:
+            raise _lib.TT2Error(f"{who}: every tensor must be on cmnd's GPU")
+        if t is not cmnd and not t.is_contiguous():
+            raise _lib.TT2Error(f"{who}: outputs, frames and pos must be contiguous")
+    g = _lib.PitchTrackArgs()
+    g.cmnd, g.frames, g.pos = cmnd.data_ptr(), ptr(frames), pos.data_ptr()
+    g.f0, g.lag, g.cost = f0.data_ptr(), lag.data_ptr(), cost.data_ptr()
+    g.cmnd_ld = ld
+    g.batch, g.t, g.tau_min, g.tau_max = B, T, tau_min, tau_max
+    g.sr, g.jump, g.switch_cost, g.unvoiced = float(sr), float(jump), float(switch), float(unvoiced)
+    L = lib()
+    need = L.tt2_pitch_track_workspace_size(B, T, tau_min, tau_max)
+    if need:
+        buf = (ws or _WS).get(need)
+        g.workspace, g.workspace_bytes = buf.data_ptr(), buf.numel()
+    check(L.tt2_pitch_track(C.byref(g), stream_ptr()), "tt2_pitch_track")
+    return f0, lag, cost
+
+
 def _drop_into(s, drop: Drop):
     s.drop_seed, s.drop_site, s.drop_thr, s.drop_scale = drop.fields()
 
