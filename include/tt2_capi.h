@@ -746,6 +746,10 @@ typedef struct tt2_bn_args {
   int32_t stats_rows;
 } tt2_bn_args;
 size_t tt2_batchnorm_workspace_size(const tt2_bn_args* a);
+/* The training forward with stats_rows = 0 keeps each chunk's mean relative to the chunk's first
+ * row of y and reads those rows again while it applies, so `out` must either be y itself (in
+ * place: same pointer, same dtype; the chunk means are then kept as absolute f32 values, which
+ * costs accuracy only where |mean| is many times the column's spread) or not overlap y at all. */
 int tt2_batchnorm_fwd(const tt2_bn_args* a, hipStream_t stream);
 int tt2_batchnorm_bwd(const tt2_bn_args* a, hipStream_t stream);
 /* SyncBatchNorm over sync_world data-parallel ranks, rank r holding its own m_r rows (ranks
@@ -753,9 +757,9 @@ int tt2_batchnorm_bwd(const tt2_bn_args* a, hipStream_t stream);
  * column sums over all sum_r m_r rows, each rank weighted by its row count; the dgamma / dbeta
  * parameter gradients stay this rank's sums, for the gradient all-reduce).
  * Each pass is two phases around a caller-issued SUM all-reduce of the first
- * sync_world * 3 * c floats of sync_buf ([W][3][c]: this rank's slot holds its moments / sums
- * and its row count m, the other slots zeros, so the reduced slots are exact and rank-ordered
- * on every rank):
+ * sync_world * 4 * c floats of sync_buf ([W][4][c]: this rank's slot holds its moments / sums,
+ * its row count m and, forward, the low part of its mean, which travels as an f32 pair; the
+ * other slots zeros, so the reduced slots are exact and rank-ordered on every rank):
  *   tt2_batchnorm_fwd_stats -> all-reduce -> tt2_batchnorm_fwd_apply   (training only)
  *   tt2_batchnorm_bwd_stats -> all-reduce -> tt2_batchnorm_bwd_apply
  * sync_world = 1 reproduces tt2_batchnorm_fwd / _bwd (no exchange needed).  The optional

@@ -343,6 +343,11 @@ __global__ __launch_bounds__(256) void ln_bwd_finalize(LnArgs a, int nb) {
 }
 
 // --------------------------------------------------------------- BatchNorm
+// floats per rank and column of the SyncBatchNorm exchange: forward (mean, M2, rows, mean -
+// (float)mean: the rank mean travels as an f32 pair, a single f32 would put its rounding into
+// the combine's n_r (mean_r - mean)^2 to first order), backward (sum dpre, sum dpre * xhat, rows, 0)
+constexpr int BN_SLOT = 4;
+
 struct BnArgs {
   const void* y; const void* dout; const void* res;
   void* out; void* dy;
@@ -353,9 +358,11 @@ struct BnArgs {
   float* dgamma; float* dbeta;
   int64_t res_ld;
   int M, C, R, rows_per, act, out_dt, res_dt, training;
+  int y_dt;   // y's element type (bn_fin64 re-reads the chunk pivots)
+  int rel;    // part's chunk means are relative to the chunk's first row of y (bn_stats_kernel's own partials)
   float eps, momentum;
   DropDesc drop;
-  // SyncBatchNorm exchange (tt2_batchnorm_{fwd,bwd}_{stats,apply}): [W][3][C] rank slots
+  // SyncBatchNorm exchange (tt2_batchnorm_{fwd,bwd}_{stats,apply}): [W][BN_SLOT][C] rank slots
   // (this rank's moments or sums and its row count, zeros in the others; all-reduced by the
   // caller) + [2][C]
   float* sync;
@@ -370,6 +377,9 @@ struct BnArgs {
 // Statistics: one workgroup per chunk of rows_per rows; CG = C/8 column groups x
 // (256/CG) row lanes.  Chunk moments use a per-column shift (the chunk's first row)
 // so sum / sum-of-squares keep full precision; chunks are combined exactly in double.
+// The chunk mean is stored relative to that shift (a.rel); bn_fin64 re-reads the shift from y
+// and, for a column whose mean dwarfs its spread, adds the two in double (see there).  Moments
+// that a GEMM epilogue produced (stats_rows > 0) hold absolute means.
 
 TT2_DEV void ld8v(const void* p, int64_t off, int dt, float (&v)[8]) {
   if (dt == TT2_BF16) ld8(reinterpret_cast<const bf16*>(p) + off, v);
@@ -409,7 +419,7 @@ __global__ __launch_bounds__(NT) void bn_stats_kernel(BnArgs a) {
       float S1 = 0.f, S2 = 0.f;
       for (int l = 0; l < nrl; ++l) { S1 += red[0][l * CG + cg][j]; S2 += red[1][l * CG + cg][j]; }
       const int c = cg * 8 + j;
-      a.part[((int64_t)blockIdx.x * 2 + 0) * a.C + c] = k[j] + S1 / n;
+      a.part[((int64_t)blockIdx.x * 2 + 0) * a.C + c] = a.rel ? S1 / n : k[j] + S1 / n;
       a.part[((int64_t)blockIdx.x * 2 + 1) * a.C + c] = fmaxf(S2 - S1 * S1 / n, 0.f);
     }
   }
@@ -425,7 +435,7 @@ constexpr int BNC_COLS = 64, BNC_G = NT / BNC_COLS;
 // bn_fin64 / bn_bsum64 combine exactly red[0..3] in a fixed order (the standalone finalize's
 // summation order, which the fused apply must reproduce bit for bit)
 static_assert(BNC_G == 4, "bn_fin64 / bn_bsum64 sum four chunk groups");
-struct BnFinScratch { double red[BNC_G][BNC_COLS]; double mu[BNC_COLS]; float mean[BNC_COLS], rstd[BNC_COLS]; };
+struct BnFinScratch { double red[BNC_G][BNC_COLS]; double mu[BNC_COLS]; float mean[BNC_COLS], rstd[BNC_COLS]; int ill[BNC_COLS]; };
 
 // forward: mean / rstd of column block cb into S.mean / S.rstd; write: also a.mean / a.rstd and
 // the running statistics (or, SyncBN, this rank's slots)
@@ -436,52 +446,77 @@ TT2_DEV void bn_fin64(const BnArgs& a, int cb, BnFinScratch& S, bool write) {
   const int cc = ok ? c : 0;
   auto nrows = [&](int r) { return (double)min(a.rows_per, a.M - r * a.rows_per); };
   auto pm = [&](int r, int w) { return a.part[((int64_t)r * 2 + w) * a.C + cc]; };
-  double acc = 0.0;
-  int r = g;
-  for (; r + 3 * BNC_G < a.R; r += 4 * BNC_G) {
-    float v[4];
+  auto piv = [&](int r) {   // the shift chunk r's mean is relative to (0: an absolute mean)
+    if (!a.rel) return 0.f;
+    const int64_t i = (int64_t)r * a.rows_per * a.C + cc;
+    return a.y_dt == TT2_BF16 ? (float)reinterpret_cast<const bf16*>(a.y)[i] : reinterpret_cast<const float*>(a.y)[i];
+  };
+  // Round 0 takes each chunk mean as the one f32 value shift + delta rounds to (what an absolute
+  // f32 mean holds).  That rounding, up to ulp(mean) / 2, enters n_c (mean_c - mean)^2 to first
+  // order: harmless while the mean is of the spread's size, but at |mean| = 1e3 sigma rstd was
+  // off by up to 60 x the error of a two-pass f32 evaluation.  A column block holding a column
+  // with |mean| > 8 sigma runs round 1, where those columns take shift + delta in double.
+  // Cost of re-reading the shifts (R strided loads of y per thread, L2-resident after the
+  // statistics pass): none measured, tt2_batchnorm_fwd with its own statistics at 12800 x 512 takes
+  // 51.6 us in f32 and 89.9 us in bf16 per call before and after (back-to-back calls, MI355X).
+  double mu = 0.0, m2 = 0.0;
+  for (int round = 0; round < 2; ++round) {
+    const bool exact = round == 1 && S.ill[cl];
+    auto mean_of = [&](float k, float v) { return exact ? (double)k + (double)v : (double)(k + v); };
+    double acc = 0.0;
+    int r = g;
+    for (; r + 3 * BNC_G < a.R; r += 4 * BNC_G) {
+      float v[4], k[4];
 #pragma unroll
-    for (int u = 0; u < 4; ++u) v[u] = pm(r + u * BNC_G, 0);
+      for (int u = 0; u < 4; ++u) { v[u] = pm(r + u * BNC_G, 0); k[u] = piv(r + u * BNC_G); }
 #pragma unroll
-    for (int u = 0; u < 4; ++u) acc += nrows(r + u * BNC_G) * v[u];
-  }
-  for (; r < a.R; r += BNC_G) acc += nrows(r) * pm(r, 0);
-  S.red[g][cl] = acc;
-  __syncthreads();
-  if (g == 0) S.mu[cl] = (((S.red[0][cl] + S.red[1][cl]) + S.red[2][cl]) + S.red[3][cl]) / a.M;
-  __syncthreads();
-  const double mu = S.mu[cl];
-  acc = 0.0;
-  r = g;
-  for (; r + 3 * BNC_G < a.R; r += 4 * BNC_G) {
-    float m1[4], m2[4];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) { m1[u] = pm(r + u * BNC_G, 0); m2[u] = pm(r + u * BNC_G, 1); }
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const double d = m1[u] - mu;
-      acc += m2[u] + nrows(r + u * BNC_G) * d * d;
+      for (int u = 0; u < 4; ++u) acc += nrows(r + u * BNC_G) * mean_of(k[u], v[u]);
     }
+    for (; r < a.R; r += BNC_G) acc += nrows(r) * mean_of(piv(r), pm(r, 0));
+    S.red[g][cl] = acc;
+    __syncthreads();
+    if (g == 0) S.mu[cl] = (((S.red[0][cl] + S.red[1][cl]) + S.red[2][cl]) + S.red[3][cl]) / a.M;
+    __syncthreads();
+    mu = S.mu[cl];
+    acc = 0.0;
+    r = g;
+    for (; r + 3 * BNC_G < a.R; r += 4 * BNC_G) {
+      float m1[4], q[4], k[4];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) { m1[u] = pm(r + u * BNC_G, 0); q[u] = pm(r + u * BNC_G, 1); k[u] = piv(r + u * BNC_G); }
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        const double d = mean_of(k[u], m1[u]) - mu;
+        acc += q[u] + nrows(r + u * BNC_G) * d * d;
+      }
+    }
+    for (; r < a.R; r += BNC_G) {
+      const double d = mean_of(piv(r), pm(r, 0)) - mu;
+      acc += pm(r, 1) + nrows(r) * d * d;
+    }
+    __syncthreads();
+    S.red[g][cl] = acc;
+    __syncthreads();
+    m2 = ((S.red[0][cl] + S.red[1][cl]) + S.red[2][cl]) + S.red[3][cl];
+    if (round == 1) break;
+    const int ill = a.rel && mu * mu * (double)a.M > 64.0 * m2;
+    __syncthreads();   // every thread has read S.red
+    if (g == 0) S.ill[cl] = ill;
+    if (!__syncthreads_or(ill)) break;
   }
-  for (; r < a.R; r += BNC_G) {
-    const double d = pm(r, 0) - mu;
-    acc += pm(r, 1) + nrows(r) * d * d;
-  }
-  __syncthreads();
-  S.red[g][cl] = acc;
-  __syncthreads();
   if (g != 0) return;
-  const double m2 = ((S.red[0][cl] + S.red[1][cl]) + S.red[2][cl]) + S.red[3][cl];
   const double n = a.M;
   const double var = m2 / n;
   S.mean[cl] = (float)mu;
   S.rstd[cl] = (float)(1.0 / sqrt(var + a.eps));
   if (!write || !ok) return;
   if (a.sync) {   // this rank's (mean, M2, rows) into its slot; the other ranks' slots zero
+    const float hi = (float)mu, lo = (float)(mu - (double)hi);
     for (int r2 = 0; r2 < a.W; ++r2) {
-      a.sync[((int64_t)r2 * 3 + 0) * a.C + c] = r2 == a.rank ? (float)mu : 0.f;
-      a.sync[((int64_t)r2 * 3 + 1) * a.C + c] = r2 == a.rank ? (float)m2 : 0.f;
-      a.sync[((int64_t)r2 * 3 + 2) * a.C + c] = r2 == a.rank ? (float)a.M : 0.f;
+      a.sync[((int64_t)r2 * BN_SLOT + 0) * a.C + c] = r2 == a.rank ? hi : 0.f;
+      a.sync[((int64_t)r2 * BN_SLOT + 1) * a.C + c] = r2 == a.rank ? (float)m2 : 0.f;
+      a.sync[((int64_t)r2 * BN_SLOT + 2) * a.C + c] = r2 == a.rank ? (float)a.M : 0.f;
+      a.sync[((int64_t)r2 * BN_SLOT + 3) * a.C + c] = r2 == a.rank ? lo : 0.f;
     }
     return;
   }
@@ -510,21 +545,21 @@ __global__ __launch_bounds__(NT) void bn_finalize_kernel(BnArgs a) {
 // SyncBatchNorm: combine the W exchanged rank moments in rank order, exactly as
 // bn_finalize_kernel combines chunks, weighted by each rank's row count n_r (ranks may hold
 // different numbers of rows): N = sum n_r, mean = sum n_r mean_r / N,
-// M2 = sum M2_r + n_r (mean_r - mean)^2.  Slots are [W][3][C]: (mean, M2, n) per rank.
+// M2 = sum M2_r + n_r (mean_r - mean)^2.  Slots are [W][BN_SLOT][C]: (mean hi, M2, n, mean lo) per rank.
 __global__ __launch_bounds__(NT) void bn_sync_finalize_kernel(BnArgs a) {
   const int c = blockIdx.x * NT + threadIdx.x;
   if (c >= a.C) return;
+  auto slot = [&](int r, int w) { return (double)a.sync[((int64_t)r * BN_SLOT + w) * a.C + c]; };
   double n = 0.0, mu = 0.0;
   for (int r = 0; r < a.W; ++r) {
-    const double nr = (double)a.sync[((int64_t)r * 3 + 2) * a.C + c];
-    n += nr;
-    mu += nr * (double)a.sync[((int64_t)r * 3 + 0) * a.C + c];
+    n += slot(r, 2);
+    mu += slot(r, 2) * (slot(r, 0) + slot(r, 3));
   }
   mu /= n;
   double m2 = 0.0;
   for (int r = 0; r < a.W; ++r) {
-    const double d = (double)a.sync[((int64_t)r * 3 + 0) * a.C + c] - mu;
-    m2 += (double)a.sync[((int64_t)r * 3 + 1) * a.C + c] + (double)a.sync[((int64_t)r * 3 + 2) * a.C + c] * d * d;
+    const double d = (slot(r, 0) + slot(r, 3)) - mu;
+    m2 += slot(r, 1) + slot(r, 2) * d * d;
   }
   const double var = m2 / n;
   a.mean[c] = (float)mu;
@@ -545,13 +580,13 @@ __global__ __launch_bounds__(NT) void bn_bwd_sync_kernel(BnArgs a) {
   if (c >= a.C) return;
   float s1 = 0.f, s2 = 0.f, n = 0.f;
   for (int r = 0; r < a.W; ++r) {
-    s1 += a.sync[((int64_t)r * 3 + 0) * a.C + c];
-    s2 += a.sync[((int64_t)r * 3 + 1) * a.C + c];
-    n += a.sync[((int64_t)r * 3 + 2) * a.C + c];
+    s1 += a.sync[((int64_t)r * BN_SLOT + 0) * a.C + c];
+    s2 += a.sync[((int64_t)r * BN_SLOT + 1) * a.C + c];
+    n += a.sync[((int64_t)r * BN_SLOT + 2) * a.C + c];
   }
-  a.sync[((int64_t)a.W * 3 + 0) * a.C + c] = s1;
-  a.sync[((int64_t)a.W * 3 + 1) * a.C + c] = s2;
-  if (c == 0) a.sync[((int64_t)a.W * 3 + 2) * a.C] = 1.f / n;
+  a.sync[((int64_t)a.W * BN_SLOT + 0) * a.C + c] = s1;
+  a.sync[((int64_t)a.W * BN_SLOT + 1) * a.C + c] = s2;
+  if (c == 0) a.sync[((int64_t)a.W * BN_SLOT + 2) * a.C] = 1.f / n;
 }
 
 // per-column constants of 8 consecutive columns
@@ -683,9 +718,10 @@ TT2_DEV void bn_bsum64(const BnArgs& a, int cb, BnBsumScratch& S, bool write) {
   a.dgamma[c] = t2;
   if (a.sync) {
     for (int r2 = 0; r2 < a.W; ++r2) {
-      a.sync[((int64_t)r2 * 3 + 0) * a.C + c] = r2 == a.rank ? t1 : 0.f;
-      a.sync[((int64_t)r2 * 3 + 1) * a.C + c] = r2 == a.rank ? t2 : 0.f;
-      a.sync[((int64_t)r2 * 3 + 2) * a.C + c] = r2 == a.rank ? (float)a.M : 0.f;
+      a.sync[((int64_t)r2 * BN_SLOT + 0) * a.C + c] = r2 == a.rank ? t1 : 0.f;
+      a.sync[((int64_t)r2 * BN_SLOT + 1) * a.C + c] = r2 == a.rank ? t2 : 0.f;
+      a.sync[((int64_t)r2 * BN_SLOT + 2) * a.C + c] = r2 == a.rank ? (float)a.M : 0.f;
+      a.sync[((int64_t)r2 * BN_SLOT + 3) * a.C + c] = 0.f;
     }
   }
 }
@@ -962,6 +998,9 @@ static BnArgs bn_args(const tt2_bn_args* p) {
   // stats_rows > 0: the workspace already holds the chunk moments (tt2_gemm col_stats)
   a.rows_per = p->stats_rows > 0 ? p->stats_rows : bn_rows_per(p->m);
   a.R = (p->m + a.rows_per - 1) / a.rows_per;
+  a.y_dt = p->dtype == TT2_DT_BF16 ? TT2_BF16 : TT2_F32;
+  // (an in-place forward, out == y, keeps absolute means: its apply overwrites the shifts)
+  a.rel = p->stats_rows <= 0 && p->out != p->y;
   a.drop = DropDesc{p->drop_seed, p->drop_site, p->drop_thr, p->drop_scale};
   a.W = 1;
   a.Mtot = p->m;
@@ -1034,12 +1073,12 @@ extern "C" int tt2_batchnorm_bwd(const tt2_bn_args* p, hipStream_t s) {
 }
 
 // ------------------------------------------------------------ SyncBatchNorm phases
-// The caller SUM-all-reduces the first W * 3 * C floats of sync_buf between the phases
+// The caller SUM-all-reduces the first W * 4 * C floats of sync_buf between the phases
 // (tt2/dist.py BnSync: RCCL in the captured step, or torch.distributed).  Every rank then
 // holds the same slots and computes the same global statistics in the same order.
 extern "C" size_t tt2_batchnorm_sync_size(const tt2_bn_args* p) {
   const int w = p->sync_world > 0 ? p->sync_world : 1;
-  return ((size_t)(3 * w + 2) * p->c + 4) * sizeof(float);   // + 1 / N (padded to 16 B)
+  return ((size_t)(BN_SLOT * w + 2) * p->c + 4) * sizeof(float);   // + 1 / N (padded to 16 B)
 }
 
 static int bn_sync_check(const tt2_bn_args* p, const char* what) {
@@ -1109,7 +1148,7 @@ extern "C" int tt2_batchnorm_bwd_apply(const tt2_bn_args* p, hipStream_t s) {
     return TT2_E_INVALID;
   BnArgs a = bn_sync_args(p);
   hipLaunchKernelGGL(bn_bwd_sync_kernel, dim3((p->c + NT - 1) / NT), dim3(NT), 0, s, a);
-  a.dbeta = a.sync + (int64_t)a.W * 3 * a.C;   // the apply reads the global sums and 1 / N
+  a.dbeta = a.sync + (int64_t)a.W * BN_SLOT * a.C;   // the apply reads the global sums and 1 / N
   a.dgamma = a.dbeta + a.C;
   a.inv_m = a.dgamma + a.C;
   const bool bf = p->dtype == TT2_DT_BF16, dbf = p->dout_dtype == TT2_DT_BF16;

@@ -297,7 +297,7 @@ class StandinGradSync(RcclGradSync):
 class BnSync:
     """SyncBatchNorm exchange (SURVEY.md:219, optional; per-replica statistics stay the
     default).  Each BatchNorm's forward moments and backward column sums leave the kernels as
-    [world][3][C] rank slots (this rank's values and its row count, zeros elsewhere: exact and
+    [world][4][C] rank slots (this rank's values, its row count and the low part of its mean, zeros elsewhere: exact and
     rank-ordered once summed, and ranks may hold different row counts), and ``exchange``
     SUM-all-reduces them between the two kernel phases (ops.batchnorm_fwd / _bwd with
     ``sync=``).
@@ -317,7 +317,7 @@ class BnSync:
         self.in_graph = grad_sync is not None
         self.snap_hook = None   # test hook: called with the slots after each in-graph exchange
         # one buffer serves every BatchNorm: stats -> exchange -> apply run in stream order
-        self._buf = torch.zeros((3 * world + 2) * self.C_MAX + 4, dtype=torch.float32, device=device)
+        self._buf = torch.zeros((4 * world + 2) * self.C_MAX + 4, dtype=torch.float32, device=device)
 
     @property
     def comm(self):
