@@ -85,7 +85,8 @@ typedef struct tt2_gemm_args {
    *   h = LN(A + a_ln_branch) (row-wise over the k = 512 columns, eps a_ln_eps) instead of A,
    *   and writes h to a_ln_out [m, k] (ld k);
    * - KV-cache scatter epilogue: when kv_cache != NULL, output columns n >= kv_col0 are also
-   *   stored to kv_cache[m * kv_bstride + (*kv_t) * kv_ld + (n - kv_col0)] (bf16). */
+   *   stored to kv_cache[m * kv_bstride + (*kv_t) * kv_ld + (n - kv_col0)] (dtype_in); a step
+   *   past the cache ((*kv_t) * kv_ld >= kv_bstride) stores nothing there. */
   const void* a_ln_branch;
   const float* a_ln_gamma;
   const float* a_ln_beta;
@@ -103,7 +104,7 @@ typedef struct tt2_gemm_args {
    *   pe_table[(*pe_t) * n_cols + n] after the rest of the epilogue (f32 table [T][n]);
    * - frame emit (the mel/stop heads GEMM): when emit_mel != NULL, with t = *emit_t < emit_tmax,
    *   columns n < emit_nmels also go to emit_mel[(m * emit_tmax + t) * emit_nmels + n] (f32) and
-   *   emit_prev[m * emit_nmels + n] (bf16, the next step's pre-net input), column emit_nmels to
+   *   emit_prev[m * emit_nmels + n] (dtype_in, the next step's pre-net input), column emit_nmels to
    *   emit_stop[m * emit_tmax + t]; the last workgroup to finish then sets *emit_t = t + 1,
    *   *emit_seed += 1 (if non-NULL) and re-zeroes *emit_done (a device int the caller zeroes
    *   once).  Replaces the tt2_decode_emit launch. */
@@ -529,13 +530,29 @@ typedef struct tt2_attn_decode_args {
   void* ln_out;
   float ln_eps;
 } tt2_attn_decode_args;
+/* Refused with TT2_E_INVALID before any launch (no output is touched): null q / k / v; batch <= 0,
+ * heads <= 0 or tk < 0; a dtype other than TT2_DT_BF16 / TT2_DT_F16 / TT2_DT_F32; head_dim != 64;
+ * q_ld, k_ld, v_ld, k_bstride or v_bstride that is not a multiple of 16 bytes; wq with a wq_ld that
+ * is not, or with heads * head_dim != 512; wo without slab, with such a wo_ld or with heads *
+ * head_dim > 512; ln_part without wq, 8 heads, ln_bias / ln_gamma / ln_beta / ln_out, q_ld == 512
+ * and a 16-bit dtype; out == NULL without wo; stop_len with neither step nor t_ptr.
+ * n_b == 0 (tk == 0, key_len[b] <= 0) gives a zero row, never NaN. */
 int tt2_attn_decode(const tt2_attn_decode_args* a, hipStream_t stream);
-/* cache[b*c_bstride + (*t_ptr)*c_ld + c] = src[b*src_ld + c], c < n */
+/* cache[b*c_bstride + (*t_ptr)*c_ld + c] = src[b*src_ld + c], c < n, b < batch; dtype TT2_DT_BF16,
+ * TT2_DT_F16 or TT2_DT_F32 (of src and cache).  A step past the cache ((*t_ptr) * c_ld >= c_bstride,
+ * i.e. *t_ptr >= t_max of a [batch][t_max][c_ld] cache) writes nothing.  Refused with TT2_E_INVALID
+ * before any launch: null src / cache / t_ptr, batch <= 0, n <= 0, any other dtype. */
 int tt2_kv_append(const void* src, int64_t src_ld, void* cache, int64_t c_bstride, int64_t c_ld, int n, int batch,
                   const int32_t* t_ptr, int dtype, hipStream_t stream);
 /* heads [batch, heads_ld] f32 -> mel_seq[b, t, :], stop_seq[b, t] (+ stop_bias[b, t] if given),
  * prev[b, :] (prev_dtype); stop_len[b] = t + 1 at the first stop logit >= stop_thr (if given);
- * then *t_ptr += 1 and *seed += 1 (seed may be NULL) */
+ * then *t_ptr += 1 and *seed += 1 (seed may be NULL), with t = *t_ptr on entry.  The first stop
+ * wins: stop_len[b] changes only while it is > t (the caller arms it with a value >= t_max, e.g.
+ * INT32_MAX), and from the step after it the frames of b are stored as zeros (mel_seq and prev;
+ * stop_seq keeps the logit).  t >= t_max: nothing is written and *t_ptr and *seed stay (the counter
+ * saturates).  Refused with TT2_E_INVALID before any launch: null heads / mel_seq / stop_seq /
+ * prev / t_ptr, batch <= 0, n_mels <= 0, t_max <= 0, heads_ld < n_mels + 1, a prev_dtype other
+ * than TT2_DT_BF16 / TT2_DT_F16 / TT2_DT_F32. */
 int tt2_decode_emit(const float* heads, int64_t heads_ld, int batch, int n_mels, int t_max, float* mel_seq,
                     float* stop_seq, void* prev, int prev_dtype, int32_t* t_ptr, uint32_t* seed,
                     const float* stop_bias, int32_t* stop_len, float stop_thr, hipStream_t stream);

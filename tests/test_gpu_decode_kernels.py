@@ -1,7 +1,8 @@
 """Decode-step kernels vs float64 torch references (GPU): the skinny-M GEMM over every
 K regime (one pass per wave slice and multi-pass), its LayerNorm prologue, KV-cache
 scatter, positional-encoding and frame-emit epilogues, and the decode attention over a
-KV cache at short and long key counts."""
+KV cache at short and long key counts.
+The exact and per-vector bars of the same kernels are in tests/test_gpu_decode_exact.py."""
 import math
 
 import pytest

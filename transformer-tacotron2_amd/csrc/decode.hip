@@ -361,6 +361,11 @@ __global__ void decode_emit_kernel(const float* heads, int64_t hld, int B, int N
 }  // namespace
 
 extern "C" int tt2_attn_decode(const tt2_attn_decode_args* p, hipStream_t s) {
+  if (!p || !p->q || !p->k || !p->v) return tt2_set_error(TT2_E_INVALID, "tt2_attn_decode: null q / k / v");
+  if (p->batch <= 0 || p->heads <= 0 || p->tk < 0)
+    return tt2_set_error(TT2_E_INVALID, "tt2_attn_decode: batch and heads must be positive, tk non-negative");
+  if (p->dtype != TT2_DT_BF16 && p->dtype != TT2_DT_F16 && p->dtype != TT2_DT_F32)
+    return tt2_set_error(TT2_E_INVALID, "tt2_attn_decode: dtype must be bf16, f16 or f32");
   if (p->head_dim != D) return tt2_set_error(TT2_E_INVALID, "tt2_attn_decode: head_dim must be 64");
   const int esz = p->dtype == TT2_DT_F32 ? 4 : 2;
   const int64_t lds[] = {p->q_ld, p->k_ld, p->v_ld, p->k_bstride, p->v_bstride};
@@ -399,10 +404,17 @@ extern "C" int tt2_attn_decode(const tt2_attn_decode_args* p, hipStream_t s) {
 
 extern "C" int tt2_kv_append(const void* src, int64_t src_ld, void* cache, int64_t c_bstride, int64_t c_ld, int n,
                              int batch, const int32_t* t_ptr, int dtype, hipStream_t s) {
+  if (!src || !cache || !t_ptr) return tt2_set_error(TT2_E_INVALID, "tt2_kv_append: null src / cache / t_ptr");
+  if (batch <= 0 || n <= 0) return tt2_set_error(TT2_E_INVALID, "tt2_kv_append: batch and n must be positive");
+  if (dtype != TT2_DT_BF16 && dtype != TT2_DT_F16 && dtype != TT2_DT_F32)
+    return tt2_set_error(TT2_E_INVALID, "tt2_kv_append: dtype must be bf16, f16 or f32");
   const int64_t total = (int64_t)batch * n;
   const int g = (int)((total + NT - 1) / NT);
   if (dtype == TT2_DT_BF16)
     hipLaunchKernelGGL(kv_append_kernel<bf16>, dim3(g), dim3(NT), 0, s, (const bf16*)src, src_ld, (bf16*)cache,
+                       c_bstride, c_ld, n, batch, t_ptr);
+  else if (dtype == TT2_DT_F16)
+    hipLaunchKernelGGL(kv_append_kernel<f16>, dim3(g), dim3(NT), 0, s, (const f16*)src, src_ld, (f16*)cache,
                        c_bstride, c_ld, n, batch, t_ptr);
   else
     hipLaunchKernelGGL(kv_append_kernel<float>, dim3(g), dim3(NT), 0, s, (const float*)src, src_ld, (float*)cache,
@@ -414,6 +426,13 @@ extern "C" int tt2_decode_emit(const float* heads, int64_t heads_ld, int batch, 
                                float* mel_seq, float* stop_seq, void* prev, int prev_dtype, int32_t* t_ptr,
                                uint32_t* seed, const float* stop_bias, int32_t* stop_len, float stop_thr,
                                hipStream_t s) {
+  if (!heads || !mel_seq || !stop_seq || !prev || !t_ptr)
+    return tt2_set_error(TT2_E_INVALID, "tt2_decode_emit: null heads / mel_seq / stop_seq / prev / t_ptr");
+  if (batch <= 0 || n_mels <= 0 || t_max <= 0 || heads_ld < (int64_t)n_mels + 1)
+    return tt2_set_error(TT2_E_INVALID, "tt2_decode_emit: batch, n_mels and t_max must be positive and "
+                                       "heads_ld >= n_mels + 1");
+  if (prev_dtype != TT2_DT_BF16 && prev_dtype != TT2_DT_F16 && prev_dtype != TT2_DT_F32)
+    return tt2_set_error(TT2_E_INVALID, "tt2_decode_emit: prev_dtype must be bf16, f16 or f32");
   if (prev_dtype == TT2_DT_BF16)
     hipLaunchKernelGGL(decode_emit_kernel<bf16>, dim3(1), dim3(NT), 0, s, heads, heads_ld, batch, n_mels, t_max,
                        mel_seq, stop_seq, (bf16*)prev, t_ptr, seed, stop_bias, stop_len, stop_thr);

@@ -107,10 +107,15 @@ def gemm_args(a, b, c, m, n, k, lda, ldb, ldc, trans_a=False, trans_b=False, bia
         table, alpha, t_ptr = pe
         g.pe_table, g.pe_alpha, g.pe_t = ptr(table), ptr(alpha), ptr(t_ptr)
     if emit is not None:
-        mel_seq, stop_seq, prev, t_ptr, seed, done, n_mels, t_max = emit
+        mel_seq, stop_seq, prev, t_ptr, seed, done, n_mels, t_max = emit[:8]
         g.emit_mel, g.emit_stop, g.emit_prev = ptr(mel_seq), ptr(stop_seq), ptr(prev)
         g.emit_t, g.emit_seed, g.emit_done = ptr(t_ptr), ptr(seed), ptr(done)
         g.emit_nmels, g.emit_tmax = n_mels, t_max
+        if len(emit) == 11:
+            stop_bias, stop_len, stop_thr = emit[8:]
+            g.emit_stop_bias, g.emit_stop_len, g.emit_stop_thr = ptr(stop_bias), ptr(stop_len), stop_thr
+        elif len(emit) != 8:
+            raise _lib.TT2Error("gemm: emit takes 8 or 11 fields")
     g.splits = max(1, splits)
     g.main_only = int(main_only)   # dev measurement: skip the split-K reduce
     if g.splits > 1:
@@ -158,7 +163,8 @@ def gemm(a, b, c, m, n, k, lda, ldb, ldc, **kw):
     kv = (cache, t_ptr, col0, bstride, ld): also store columns >= col0 to the KV cache at step *t_ptr.
     pe = (table, alpha, t_ptr): add alpha * table[*t_ptr] to every output row (skinny path).
     emit = (mel_seq, stop_seq, prev, t_ptr, seed, done, n_mels, t_max): the decode frame emit
-    (see tt2_capi.h), which also advances *t_ptr.
+    (see tt2_capi.h), which also advances *t_ptr; three more fields, (..., stop_bias, stop_len, stop_thr),
+    set its stop handling (emit_stop_bias / emit_stop_len / emit_stop_thr; either tensor may be None).
     col_stats (f32, 2 * ceil(m / rows) * n, rows = gemm_stats_rows(...)): the stored C's column
     moments per chunk (mean, M2), for batchnorm_fwd(stats=(col_stats, rows)).
     bn_bwd (bn_bwd_args(...)): C is that BatchNorm backward's dout; its per-chunk sums go to the
