@@ -1,4 +1,4 @@
-"""References, problem builders and checkers of the fused attention kernels (csrc/attention.hip),
+"""References, problem builders and checkers of the fused attention kernels (csrc/attention*.hip),
 written from the contract in include/tt2_capi.h.  Everything runs on the CPU; the tensors of a
 problem are float64 [B, H, T, 64].  tests/test_attn_refs.py validates this file against torch's
 own attention and autograd and proves with mutants that the checkers bite;

@@ -240,7 +240,7 @@ def test_parts_refused_off_the_plain_launch(causal, dtype, parts, monkeypatch):
 @pytest.mark.parametrize("case", R.cases(R.RANDOM_ROT), ids=lambda c: c[0])
 def test_repeatable(case, variant):
     """Forward and backward run twice give bit-identical O, LSE, dQ, dK, dV (no atomics: the
-    file header of attention.hip promises it), guards included."""
+    file header of attention_common.h promises it), guards included."""
     p, _, _, _ = reference("random", case, variant)
     a, b = Launch(p, variant), Launch(p, variant)
     a.run()

@@ -1,5 +1,6 @@
-// In-kernel timeline of the v3 attention forward (dev tool): builds attention.hip with its
-// stamp hooks defined (s_memtime per wave), runs the decoder's causal self-attention shape
+// In-kernel timeline of the v3 attention forward (dev tool): builds attention_fwd3.hip with its
+// stamp hooks defined (s_memtime per wave; the other attention units beside it, so that
+// tt2_attn_fwd links), runs the decoder's causal self-attention shape
 // (B = 16, H = 8, 800 x 800, d 64) and prints, per query block, the average per-tile split of
 // its waves: S + row max, softmax + PV issue, next-tile LDS write (its loads' wait), barrier.
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -I include -I transformer-tacotron2_amd/csrc \
@@ -14,6 +15,10 @@ __device__ unsigned long long g_st[ST_N];
 #define ATTN_STAMP(slot)                                                                              \
   if ((threadIdx.x & 63) == 0 && (slot) < 64 && blockIdx.x < 256 && blockIdx.y < 8 && (threadIdx.x >> 6) < 4) \
     g_st[(((size_t)blockIdx.y * 256 + blockIdx.x) * 4 + (threadIdx.x >> 6)) * 64 + (slot)] = __builtin_amdgcn_s_memtime();
+#include "../transformer-tacotron2_amd/csrc/attention_fwd3.hip"
+#include "../transformer-tacotron2_amd/csrc/attention_v1.hip"
+#include "../transformer-tacotron2_amd/csrc/attention_bwd3.hip"
+#include "../transformer-tacotron2_amd/csrc/attention_align.hip"
 #include "../transformer-tacotron2_amd/csrc/attention.hip"
 #include "../transformer-tacotron2_amd/csrc/runtime.cpp"
 

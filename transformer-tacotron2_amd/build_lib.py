@@ -20,12 +20,18 @@ OUT = os.path.join(PKG, "tt2", "libtt2.so")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-I" + INCLUDE, "-I" + CSRC,
          "-Wno-unused-result"]
-# Per-file extras.  Attention keeps MFMA accumulators in arch VGPRs: its softmax reads
-# and rescales them every tile, and the default AGPR placement adds a copy per use.
-EXTRA = {"attention.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"],
-         "attention_mono.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"],
-         # YIN's difference loop as plain f32 subtracts and fmas: packed, it measured slower
+# Per-file extras.
+EXTRA = {  # YIN's difference loop as plain f32 subtracts and fmas: packed, it measured slower
          "pitch.hip": ["-fno-slp-vectorize"]}
+
+
+def extra_flags(name: str) -> list[str]:
+    """Per-file extras of csrc/<name>.  Every attention unit (attention*.hip) keeps MFMA accumulators
+    in arch VGPRs: the softmax reads and rescales them every tile, and the default AGPR placement
+    adds a copy per use."""
+    if name.startswith("attention") and name.endswith(".hip"):
+        return ["-mllvm", "-amdgpu-mfma-vgpr-form=1"]
+    return EXTRA.get(name, [])
 
 
 def _headers_mtime() -> float:
@@ -43,8 +49,7 @@ ASAN_OUT = os.path.join(ASAN_BUILD, "libtt2_asan.so")
 
 
 def _compile(src: str, obj: str, asan: bool = False) -> tuple[str, int, str]:
-    cmd = [HIPCC] + FLAGS + (ASAN_FLAGS if asan else []) + EXTRA.get(os.path.basename(src), []) + ["-c", src,
-                                                                                                  "-o", obj]
+    cmd = [HIPCC] + FLAGS + (ASAN_FLAGS if asan else []) + extra_flags(os.path.basename(src)) + ["-c", src, "-o", obj]
     r = subprocess.run(cmd, capture_output=True, text=True)
     return src, r.returncode, r.stdout + r.stderr
 

@@ -1,31 +1,11 @@
 // attention_mono.hip -- monotonic alignment search over the raw attention scores of forwards
 // already run (tt2_align_monotonic; head dim 64, gfx950).  A translation unit of its own, so
-// that the device code of attention.hip stays what it was; the score products reuse the v3
-// forward's building blocks (attention_v3.h).
-#include <math.h>
-
-#include <string>
-#include <type_traits>
-
-#include "tt2_capi.h"
-#include "tt2_internal.h"
-#include "tt2_common.h"
-
-namespace {
-
-constexpr int D = 64;     // head dim
-constexpr float LOG2E = 1.4426950408889634f;
-
+// that the device code of the other attention units stays what it was (it has its
+// entry points with it); the score products reuse the v3 forward's building blocks
+// (attention_v3.h).
 #include "attention_v3.h"
 
-int attn_err(const char* who, const char* msg) {
-  return tt2_set_error(TT2_E_INVALID, (std::string(who) + ": " + msg).c_str());
-}
-TT2_DEV int align_qlim(const int32_t* q_len, int tq, int b) {   // as attention.hip's
-  int ql = tq;
-  if (q_len) ql = min(ql, q_len[b]);
-  return ql < 0 ? 0 : ql;
-}
+namespace {
 
 // ---------------------------------------------------------- monotonic alignment search
 // Viterbi over the raw scores of one (layer, head) per utterance (tt2_capi.h states the
@@ -112,10 +92,8 @@ __global__ __launch_bounds__(MONO_NT) void align_mono_kernel(tt2_align_mono_args
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const int ql = lane & 31, hi = lane >> 5;
   const int b = blockIdx.x;
-  const int Ty = align_qlim(a.q_len, a.tq, b);
-  int Tx = a.tk;
-  if (a.key_len) Tx = min(Tx, a.key_len[b]);
-  Tx = Tx < 0 ? 0 : Tx;
+  const int Ty = len_limit(a.tq, a.q_len, b);
+  const int Tx = len_limit(a.tk, a.key_len, b);
   const int Te = min(Tx, Ty);
   const int li = a.sel ? a.sel[2 * b] : a.sel_layer;
   const int h = a.sel ? a.sel[2 * b + 1] : a.sel_head;

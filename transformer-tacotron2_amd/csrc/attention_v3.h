@@ -1,9 +1,26 @@
-// attention_v3.h -- the v3 (32x32x16 bf16 MFMA) building blocks shared by attention.hip and
-// attention_mono.hip: accumulator type, tile swizzle, buffer views, register-staged tile copies,
-// operand fragments.  Included INSIDE the including file's anonymous namespace, after
-// `constexpr int D = 64;` (head dim) and tt2_common.h: no include guard business beyond the
-// pragma, no namespace of its own.
+// attention_v3.h -- the v3 (32x32x16 bf16 MFMA) building blocks shared by the v3 forward, the v3
+// backward, the alignment statistics and the monotonic search (attention_fwd3.hip,
+// attention_bwd3.hip, attention_align.hip, attention_mono.hip): accumulator type, tile swizzle,
+// buffer views, register-staged tile copies, operand fragments.
+//
+// v3 kernels (bf16): v_mfma_f32_32x32x16_bf16 with "swapped" products.  Every product
+// puts the streamed dimension (keys in dQ / forward, queries in dK-dV) on the MFMA rows
+// and the wave's own 32 rows (queries, or keys) on the lane:
+//   forward  S^T = K Q^T      O^T  += V^T  P^T
+//   dQ       S^T = K Q^T, dP^T = V dO^T,   dQ^T += K^T dS^T
+//   dK, dV   S   = Q K^T, dP  = dO V^T,    dV^T += dO^T P,  dK^T += Q^T dS
+// The 32x32 accumulator then holds, per lane, 16 streamed rows crow(r, hi) =
+// (r&3) + 8(r>>2) + 4hi of ONE own row, and those 16 values ARE the B operand of the
+// next product once its A operand is read transposed (ds_read_b64_tr_b16) from rows
+// base + {4hi + 0..3} and base + {8 + 4hi + 0..3}.  P and dS never leave registers,
+// softmax statistics are per lane (one xor-32 shuffle per tile), and each LDS fragment
+// feeds a 32-row MFMA (32 FLOP per LDS byte: the LDS array is not the bound).
+// Tiles are 64 rows x 64 bf16 in LDS with the chunk swizzle below, double-buffered and
+// register-staged (global loads for tile t+1 in flight while tile t computes).
 #pragma once
+#include "attention_common.h"
+
+namespace {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
@@ -111,3 +128,5 @@ TT2_DEV void zero16(f32x16& x) {
 #pragma unroll
   for (int i = 0; i < 16; ++i) x[i] = 0.f;
 }
+
+}  // namespace
