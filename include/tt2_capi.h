@@ -486,6 +486,46 @@ typedef struct tt2_pitch_track_args {
 size_t tt2_pitch_track_workspace_size(int batch, int t, int tau_min, int tau_max);
 int tt2_pitch_track(const tt2_pitch_track_args* a, hipStream_t stream);
 
+/* Sample-rate conversion by a rational factor up / down with a polyphase FIR bank: one launch for a
+ * batch of utterances, no host synchronisation.  For sr_in -> sr_out, g = gcd(sr_in, sr_out),
+ * up = sr_out / g and down = sr_in / g.  `bank` is [up, bank_ld] f32: row r holds the 2 * half + 1
+ * taps of the outputs n with n mod up = r, tap k = -half .. half at column k + half.  The bank is the
+ * caller's; tt2.audio.resample_bank designs the Kaiser-windowed sinc
+ *   h(t) = c sinc(c t) w(c t / zeros),  c = rolloff * min(1, up / down),  sinc(x) = sin(pi x) / (pi x),
+ *   w(u) = I0(beta sqrt(1 - u^2)) / I0(beta) for |u| < 1, else 0,  half = ceil(zeros / c),
+ *   bank[r][k + half] = h(k - f_r),  f_r = ((r * down) mod up) / up,
+ * in float64, rounded once to f32.  For utterance b, len_b = clamp(lens[b], 0, n_in) (lens NULL:
+ * n_in) and out_b = min(ceil(len_b * up / down), n_out), the ceiling in 64-bit arithmetic.  For
+ * n = q * up + r < out_b, with i0 = q * down + floor(r * down / up) (= floor(n * down / up)),
+ *   y[b][n] = sum_{k = -half .. half} bank[r][k + half] * x[b][i0 + k],
+ * where a sample with i0 + k outside [0, len_b) counts as 0 and is not read.  All arithmetic is f32.
+ * The sum is one accumulator that starts at +0 and takes k ascending from -half to half with one fma
+ * per tap (the product is not rounded), the taps of samples outside the utterance included (an fma
+ * with 0).  The order does not depend on the tiling, so an output value does not depend on batch,
+ * n_out or the utterance's position in the batch; results are bit-identical run to run (no atomics),
+ * and where every product and partial sum is exactly representable every output bit is defined by
+ * the above.  y[b][n] is exactly 0 for out_b <= n < n_out; nothing is written at or past column
+ * n_out of a row; out_lens[b] = out_b when out_lens is given.  No sample at an index >= len_b is
+ * read, and no element outside [0, x_ld) of a row.  Every index that can reach n * down is 64-bit.
+ * Refused with TT2_E_INVALID before any launch: up < 1, down < 1 or up > TT2_RESAMPLE_MAX_PHASES;
+ * half < 0 or 2 * half + 1 > TT2_RESAMPLE_MAX_TAPS; batch, n_in or n_out negative; x_ld < n_in,
+ * y_ld < n_out or bank_ld < 2 * half + 1; a null bank or y, or a null x with samples to read
+ * (batch, n_out and n_in all positive); more than 2^31 - 1 work groups.  batch = 0 or n_out = 0
+ * succeeds without a launch (out_lens is then not written); n_in = 0 with n_out > 0 launches and
+ * zero-fills. */
+#define TT2_RESAMPLE_MAX_TAPS   256   /* 2*half + 1 */
+#define TT2_RESAMPLE_MAX_PHASES 1024  /* up */
+typedef struct tt2_resample_args {
+  const float* x;          /* [batch, x_ld] */
+  const int32_t* lens;     /* [batch] valid input samples, device, or NULL (= n_in) */
+  const float* bank;       /* [up, bank_ld] f32, row r = taps k = -half..half */
+  float* y;                /* [batch, y_ld] */
+  int32_t* out_lens;       /* optional [batch] */
+  int64_t x_ld, y_ld, bank_ld;
+  int32_t batch, n_in, n_out, up, down, half;
+} tt2_resample_args;
+int tt2_resample(const tt2_resample_args* a, hipStream_t stream);
+
 /* ------------------------------------------------------------------ decode
  * One query row per batch element (the AR decode step):
  * out[b*o_ld + 64h ..] = softmax(scale q k^T) v over keys j < n_b of batch b,

@@ -289,6 +289,23 @@ SIGNATURES.update({
 })
 
 
+RESAMPLE_MAX_TAPS, RESAMPLE_MAX_PHASES = 256, 1024   # TT2_RESAMPLE_MAX_TAPS / _MAX_PHASES
+
+
+class ResampleArgs(C.Structure):
+    """tt2_resample_args: polyphase sample-rate conversion of a batch of utterances."""
+    _fields_ = [
+        ("x", vp), ("lens", vp), ("bank", vp), ("y", vp), ("out_lens", vp),
+        ("x_ld", i64), ("y_ld", i64), ("bank_ld", i64),
+        ("batch", i32), ("n_in", i32), ("n_out", i32), ("up", i32), ("down", i32), ("half", i32),
+    ]
+
+
+SIGNATURES.update({
+    "tt2_resample": ([C.POINTER(ResampleArgs), vp], C.c_int),
+})
+
+
 class ReduceArgs(C.Structure):
     _fields_ = [("src", vp), ("dst", vp), ("ld", i64), ("rows", i32), ("cols", i32), ("beta", f32)]
 

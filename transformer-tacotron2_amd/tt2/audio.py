@@ -12,6 +12,10 @@
   for the phoneme-level pitch and energy of a duration-based student.
 * ``PitchTracker``: the same, with F0 and voicing from one Viterbi path per utterance through
   the lags and an unvoiced state over YIN's d' (tt2_pitch_track) instead of a decision per frame.
+* ``Resampler`` / ``resample_bank``: waveform batch at any integer rate -> 22.05 kHz (or any other
+  rate) by a polyphase Kaiser-windowed sinc bank designed in float64 on the host (tt2_resample, one
+  launch per batch): the step in front of everything above for corpora that ship at 24, 44.1 or
+  48 kHz.
 
 Every transform runs on the GPU through libtt2: the window-folded DFT basis, its
 inverse and the mel filterbank are f32 ``tt2_gemm`` operands (constant tables built
@@ -306,6 +310,108 @@ class PitchTracker:
 
     def __call__(self, audio: torch.Tensor, lens: torch.Tensor | None = None) -> Pitch:
         return self.track(audio, lens).pitch
+
+
+class ResampleBank(NamedTuple):
+    """resample_bank(): the polyphase filter bank of one rate pair."""
+    up: int
+    down: int
+    half: int
+    taps: torch.Tensor           # [up, 2 * half + 1] float64, host
+
+
+def resample_bank(sr_in: int, sr_out: int, zeros: int = 24, rolloff: float = 0.9, beta: float = 10.0) -> ResampleBank:
+    """The Kaiser-windowed sinc bank of tt2_resample for sr_in -> sr_out (include/tt2_capi.h has
+    the definition): up = sr_out / g, down = sr_in / g, cutoff c = rolloff * min(1, up / down) of
+    the input Nyquist, `zeros` zero crossings either side, half = ceil(zeros / c) taps either side.
+    Row r holds h(k - f_r), k = -half .. half, f_r = ((r * down) mod up) / up.  float64 on the
+    host, no device work.  The defaults (24 zeros, rolloff 0.9, beta 10) keep a tone below 0.726 of
+    the lower Nyquist within 6e-6 and one above 1.15 of the new Nyquist below -105 dB."""
+    from ._lib import RESAMPLE_MAX_PHASES, RESAMPLE_MAX_TAPS
+    if int(sr_in) != sr_in or int(sr_out) != sr_out or sr_in < 1 or sr_out < 1:
+        raise ValueError(f"resample_bank: rates must be positive integers, got {sr_in} -> {sr_out}")
+    if int(zeros) != zeros or zeros < 1:
+        raise ValueError(f"resample_bank: zeros must be an integer >= 1, got {zeros}")
+    if not (0.0 < rolloff <= 1.0):
+        raise ValueError(f"resample_bank: rolloff must be in (0, 1], got {rolloff}")
+    if not (math.isfinite(beta) and beta >= 0.0):
+        raise ValueError(f"resample_bank: beta must be finite and not negative, got {beta}")
+    sr_in, sr_out, zeros = int(sr_in), int(sr_out), int(zeros)
+    g = math.gcd(sr_in, sr_out)
+    up, down = sr_out // g, sr_in // g
+    c = float(rolloff) * min(1.0, up / down)
+    half = math.ceil(zeros / c)
+    if up > RESAMPLE_MAX_PHASES:
+        raise ValueError(f"resample_bank: {sr_in} -> {sr_out} needs {up} phases, above "
+                         f"TT2_RESAMPLE_MAX_PHASES = {RESAMPLE_MAX_PHASES}")
+    if 2 * half + 1 > RESAMPLE_MAX_TAPS:
+        raise ValueError(f"resample_bank: {sr_in} -> {sr_out} with {zeros} zeros needs {2 * half + 1} taps, above "
+                         f"TT2_RESAMPLE_MAX_TAPS = {RESAMPLE_MAX_TAPS}")
+    d = torch.float64
+    r = torch.arange(up, dtype=torch.int64)
+    f = ((r * down) % up).to(d) / up
+    t = torch.arange(-half, half + 1, dtype=d)[None, :] - f[:, None]     # [up, K], input samples
+    u = c * t / zeros
+    inside = u.abs() < 1.0
+    w = torch.special.i0(beta * torch.sqrt((1.0 - u * u).clamp_min(0.0))) / torch.special.i0(torch.tensor(beta, dtype=d))
+    taps = c * torch.sinc(c * t) * torch.where(inside, w, torch.zeros((), dtype=d))
+    return ResampleBank(up, down, half, taps)
+
+
+class Resampler:
+    """Sample-rate conversion sr_in -> sr_out (tt2_resample; include/tt2_capi.h has the definition)
+    of a padded batch, with the bank of resample_bank rounded once to f32.  The corpus tool
+    (tools/resample_corpus.py) and data.collate(resampler=) run it; MelExtractor, PitchExtractor
+    and everything after them stay at 22.05 kHz."""
+
+    def __init__(self, sr_in: int, sr_out: int = SR, device="cuda", zeros: int = 24, rolloff: float = 0.9,
+                 beta: float = 10.0):
+        self.bank = resample_bank(sr_in, sr_out, zeros, rolloff, beta)
+        self.sr_in, self.sr_out = int(sr_in), int(sr_out)
+        self.zeros, self.rolloff, self.beta = int(zeros), float(rolloff), float(beta)
+        self.dev = torch.device(device)
+        self._taps = None
+
+    up = property(lambda self: self.bank.up)
+    down = property(lambda self: self.bank.down)
+    half = property(lambda self: self.bank.half)
+
+    def params(self) -> dict:
+        return {"sr_in": self.sr_in, "sr_out": self.sr_out, "up": self.up, "down": self.down, "half": self.half,
+                "zeros": self.zeros, "rolloff": self.rolloff, "beta": self.beta}
+
+    def taps(self) -> torch.Tensor:
+        """The bank on the device, [up, 2 * half + 1] f32 (uploaded on first use)."""
+        if self._taps is None:
+            self._taps = self.bank.taps.float().to(self.dev)
+        return self._taps
+
+    def out_len(self, n: int) -> int:
+        return -(-int(n) * self.up // self.down)
+
+    def __call__(self, audio: torch.Tensor, lens: torch.Tensor | None = None):
+        """audio [B, L] f32, lens [B] samples (optional) -> (audio_out [B, ceil(L * up / down)] f32,
+        out_lens [B] int32 = ceil(lens * up / down)); samples past an utterance's out_len are 0.
+        One tt2_resample launch on the current stream into fresh tensors; no host synchronisation.
+        With sr_in == sr_out the inputs are returned as they are (lens as an int32 tensor of L when
+        None) and nothing is launched."""
+        B, L = audio.shape
+        if self.up == self.down:
+            if lens is None:
+                lens = torch.full((B,), L, dtype=torch.int32, device=audio.device)
+            return audio, lens
+        audio = audio.to(self.dev, torch.float32)
+        if audio.stride(1) != 1 and L > 1:
+            audio = audio.contiguous()
+        lens32 = lens.to(self.dev, torch.int32).contiguous() if lens is not None else None
+        n_out = self.out_len(L)
+        if B == 0 or n_out == 0:
+            return (torch.zeros(B, n_out, dtype=torch.float32, device=self.dev),
+                    torch.zeros(B, dtype=torch.int32, device=self.dev))
+        y = torch.empty(B, n_out, dtype=torch.float32, device=self.dev)
+        out_lens = torch.empty(B, dtype=torch.int32, device=self.dev)
+        ops.resample(audio, y, self.taps(), self.up, self.down, self.half, lens=lens32, out_lens=out_lens)
+        return y, out_lens
 
 
 def phoneme_average(values: torch.Tensor, durations: torch.Tensor, mask: torch.Tensor | None = None) -> torch.Tensor:

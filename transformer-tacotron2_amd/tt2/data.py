@@ -15,6 +15,11 @@
 * ``extract_durations``: per-utterance phoneme durations from a trained model's alignment
   (``TransformerTTS.durations``), written as ``<id>.npy`` plus a ``durations.json`` manifest:
   the training targets of a non-autoregressive student.
+* ``read_wav`` / ``LJSpeech(root, sr=...)`` / ``collate(..., resampler=)`` / ``resample_corpus``:
+  corpora at other rates (LibriTTS 24 kHz, VCTK 48 kHz).  ``load_wav`` still refuses a file that is
+  not at the rate it is asked for; ``resample_corpus`` (``tools/resample_corpus.py``) rewrites a
+  corpus at 22.05 kHz through ``tt2.audio.Resampler``, and ``collate`` can run the same resampler on
+  the fly.  Everything downstream (mels, pitch, durations, MCD) stays at 22.05 kHz.
 """
 from __future__ import annotations
 
@@ -57,24 +62,33 @@ def ids_to_text(ids) -> str:
     return "".join(SYMBOLS[i] for i in ids if 0 < i < len(SYMBOLS) and SYMBOLS[i] != EOS)
 
 
-def load_wav(path: str, sr: int = 22050) -> np.ndarray:
-    """Mono float32 in [-1, 1] (PCM16 / PCM32 / float WAV); no resampling."""
+def read_wav(path: str) -> tuple[np.ndarray, int]:
+    """(mono float32 in [-1, 1], rate) of a PCM16 / PCM32 / float WAV, at the file's own rate:
+    load_wav's conversions, unchanged.  (Channels are averaged before the integer scaling is
+    chosen, so a multi-channel PCM file comes out unscaled, as it always did from load_wav.)"""
     from scipy.io import wavfile
     rate, x = wavfile.read(path)
-    if rate != sr:
-        raise ValueError(f"{path}: {rate} Hz, expected {sr} (resample offline)")
     if x.ndim > 1:
         x = x.mean(axis=1)
     if x.dtype == np.int16:
-        return (x / 32768.0).astype(np.float32)
+        return (x / 32768.0).astype(np.float32), int(rate)
     if x.dtype == np.int32:
-        return (x / 2147483648.0).astype(np.float32)
-    return x.astype(np.float32)
+        return (x / 2147483648.0).astype(np.float32), int(rate)
+    return x.astype(np.float32), int(rate)
+
+
+def load_wav(path: str, sr: int = 22050) -> np.ndarray:
+    """Mono float32 in [-1, 1] (PCM16 / PCM32 / float WAV); no resampling."""
+    x, rate = read_wav(path)
+    if rate != sr:
+        raise ValueError(f"{path}: {rate} Hz, expected {sr} (resample offline: tools/resample_corpus.py)")
+    return x
 
 
 class LJSpeech:
-    def __init__(self, root: str, use_normalized: bool = True):
+    def __init__(self, root: str, use_normalized: bool = True, sr: int = 22050):
         self.root = root
+        self.sr = int(sr)   # the rate of the corpus' files: wav() refuses any other
         self.items = []   # (id, text)
         with open(os.path.join(root, "metadata.csv"), encoding="utf-8", newline="") as f:
             for row in csv.reader(f, delimiter="|", quoting=csv.QUOTE_NONE):
@@ -88,7 +102,7 @@ class LJSpeech:
         return len(self.items)
 
     def wav(self, i: int) -> np.ndarray:
-        return load_wav(os.path.join(self.root, "wavs", self.items[i][0] + ".wav"))
+        return load_wav(os.path.join(self.root, "wavs", self.items[i][0] + ".wav"), self.sr)
 
     def ids(self, i: int) -> list[int]:
         return text_to_ids(self.items[i][1])
@@ -112,9 +126,14 @@ def bucket_batches(lengths, batch_size: int, bucket_mult: int = 8, seed: int = 0
     return batches
 
 
-def collate(ds: LJSpeech, indices, extractor, device="cuda"):
+def collate(ds: LJSpeech, indices, extractor, device="cuda", resampler=None):
     """(text [B, Tx] i64, text_len [B], mel [B, T, 80] f32, mel_len [B]) for one batch;
-    the log-mels come from one batched GPU STFT (tt2.audio.MelExtractor)."""
+    the log-mels come from one batched GPU STFT (tt2.audio.MelExtractor).  With a resampler (a
+    tt2.audio.Resampler whose sr_in is the corpus' rate ds.sr) the uploaded batch goes through it
+    first and the extractor sees its output and output lengths."""
+    if resampler is not None and int(resampler.sr_in) != int(getattr(ds, "sr", 22050)):
+        raise ValueError(f"collate: the resampler reads {resampler.sr_in} Hz, the corpus is at "
+                         f"{getattr(ds, 'sr', 22050)} Hz")
     ids = [ds.ids(i) for i in indices]
     wavs = [ds.wav(i) for i in indices]
     B = len(indices)
@@ -128,7 +147,10 @@ def collate(ds: LJSpeech, indices, extractor, device="cuda"):
     for b, w in enumerate(wavs):
         audio[b, :len(w)] = torch.from_numpy(w)
     lens = torch.tensor([len(w) for w in wavs], dtype=torch.int32)
-    mel, frames = extractor(audio.to(device), lens.to(device))
+    audio, lens = audio.to(device), lens.to(device)
+    if resampler is not None:
+        audio, lens = resampler(audio, lens)
+    mel, frames = extractor(audio, lens)
     return text.to(device), text_len.to(device), mel, frames.to(torch.long)
 
 
@@ -267,5 +289,49 @@ def extract_pitch(batches, out_dir: str, extractor, durations_dir: str | None = 
         mean = s / cnt if cnt else 0.0
         manifest[key] = {"mean": mean, "std": max(s2 / cnt - mean * mean, 0.0) ** 0.5 if cnt else 0.0, "frames": cnt}
     with open(os.path.join(out_dir, "pitch.json"), "w") as f:
+        json.dump(manifest, f, indent=1, sort_keys=True)
+    return manifest
+
+
+def resample_corpus(ds: LJSpeech, out_root: str, resampler, batch_size: int = 16):
+    """The corpus `ds` at the resampler's output rate, as a corpus of the same layout under
+    out_root: out_root/wavs/<id>.wav (PCM16 mono at sr_out: rint(x * 32768) clipped to
+    [-32768, 32767]), a copy of metadata.csv, and out_root/resample.json: {"resampler": its
+    params(), "utterances": {id: {"samples_in", "samples_out", "clipped"}}} with `clipped` the
+    number of samples the PCM16 range cut.  `resampler` is a tt2.audio.Resampler whose sr_in is
+    ds.sr, or any callable (audio [B, L], lens [B]) -> (audio_out, out_lens) with sr_in, sr_out and
+    params(): one call per batch of batch_size utterances in corpus order.  Returns the manifest."""
+    import shutil
+    from scipy.io import wavfile
+    if int(resampler.sr_in) != int(getattr(ds, "sr", 22050)):
+        raise ValueError(f"resample_corpus: the resampler reads {resampler.sr_in} Hz, the corpus is at "
+                         f"{getattr(ds, 'sr', 22050)} Hz")
+    if batch_size < 1:
+        raise ValueError("resample_corpus: batch_size must be at least 1")
+    if os.path.abspath(out_root) == os.path.abspath(ds.root):
+        raise ValueError("resample_corpus: out_root is the corpus itself")
+    os.makedirs(os.path.join(out_root, "wavs"), exist_ok=True)
+    dev = getattr(resampler, "dev", "cpu")
+    manifest = {"resampler": resampler.params() if hasattr(resampler, "params") else {}, "utterances": {}}
+    for s in range(0, len(ds), batch_size):
+        idx = list(range(s, min(s + batch_size, len(ds))))
+        wavs = [ds.wav(i) for i in idx]
+        audio = torch.zeros(len(idx), max(len(w) for w in wavs), dtype=torch.float32)
+        for b, w in enumerate(wavs):
+            audio[b, :len(w)] = torch.from_numpy(w)
+        lens = torch.tensor([len(w) for w in wavs], dtype=torch.int32)
+        y, out_lens = resampler(audio.to(dev), lens.to(dev))
+        y = y.detach().float().cpu().numpy()
+        out_lens = [int(n) for n in torch.as_tensor(out_lens).cpu()]
+        for b, i in enumerate(idx):
+            uid = ds.items[i][0]
+            q = np.rint(y[b, :out_lens[b]].astype(np.float64) * 32768.0)
+            clipped = int(((q < -32768) | (q > 32767)).sum())
+            wavfile.write(os.path.join(out_root, "wavs", uid + ".wav"), int(resampler.sr_out),
+                          np.clip(q, -32768, 32767).astype(np.int16))
+            manifest["utterances"][str(uid)] = {"samples_in": len(wavs[b]), "samples_out": out_lens[b],
+                                                "clipped": clipped}
+    shutil.copyfile(os.path.join(ds.root, "metadata.csv"), os.path.join(out_root, "metadata.csv"))
+    with open(os.path.join(out_root, "resample.json"), "w") as f:
         json.dump(manifest, f, indent=1, sort_keys=True)
     return manifest

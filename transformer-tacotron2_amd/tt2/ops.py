@@ -707,6 +707,54 @@ def pitch_track(cmnd, frames, f0, lag, cost, tau_min, tau_max, sr, pos, jump, sw
     return f0, lag, cost
 
 
+def resample(x, y, bank, up, down, half, lens=None, out_lens=None):
+    """Polyphase sample-rate conversion (tt2_resample_args): x [B, n_in] f32 -> y [B, n_out] f32 by
+    the factor up / down with bank [up, >= 2 * half + 1] f32 (row r: the taps of the outputs
+    n = r mod up).  x, y and bank are 2-D with a contiguous last dim (row views are fine).  lens [B]
+    int32 bounds the valid samples of each utterance (None: n_in); out_lens [B] int32, when given,
+    receives min(ceil(len * up / down), n_out).  Outputs past that are 0.  On the current stream, no
+    host synchronisation.  Deterministic."""
+    who = "resample"
+    up, down, half = int(up), int(down), int(half)
+    if not (1 <= up <= _lib.RESAMPLE_MAX_PHASES) or down < 1:
+        raise _lib.TT2Error(f"{who}: 1 <= up <= {_lib.RESAMPLE_MAX_PHASES} and down >= 1, got {up} / {down}")
+    K = 2 * half + 1
+    if half < 0 or K > _lib.RESAMPLE_MAX_TAPS:
+        raise _lib.TT2Error(f"{who}: 2 * half + 1 = {K} taps outside 1 .. {_lib.RESAMPLE_MAX_TAPS}")
+    for name, t in (("x", x), ("y", y), ("bank", bank)):
+        if t.dtype != torch.float32 or t.dim() != 2 or (t.shape[1] > 1 and t.stride(1) != 1):
+            raise _lib.TT2Error(f"{who}: {name} must be f32 [rows, cols] with a contiguous last dim")
+    if x.shape[0] != y.shape[0]:
+        raise _lib.TT2Error(f"{who}: x has {x.shape[0]} rows, y {y.shape[0]}")
+    B, n_in = x.shape
+    n_out = y.shape[1]
+    if bank.shape[0] != up or bank.shape[1] < K:
+        raise _lib.TT2Error(f"{who}: bank must be [{up}, >= {K}], got {list(bank.shape)}")
+
+    def ld(t):   # a single row's stride is arbitrary: any value that covers the row
+        return t.stride(0) if t.shape[0] > 1 else max(t.stride(0), t.shape[1])
+
+    for name, t in (("x", x), ("y", y), ("bank", bank)):
+        if ld(t) < t.shape[1]:
+            raise _lib.TT2Error(f"{who}: {name}'s rows overlap (stride {t.stride(0)} below {t.shape[1]} columns)")
+    tensors = [x, y, bank]
+    for name, t in (("lens", lens), ("out_lens", out_lens)):
+        if t is not None:
+            _need(f"{who}: {name}", t, B, torch.int32)
+            if not t.is_contiguous():
+                raise _lib.TT2Error(f"{who}: {name} must be contiguous")
+            tensors.append(t)
+    for t in tensors:
+        if t.device != y.device or not t.is_cuda:
+            raise _lib.TT2Error(f"{who}: every tensor must be on y's GPU")
+    g = _lib.ResampleArgs()
+    g.x, g.lens, g.bank, g.y, g.out_lens = x.data_ptr(), ptr(lens), bank.data_ptr(), y.data_ptr(), ptr(out_lens)
+    g.x_ld, g.y_ld, g.bank_ld = ld(x), ld(y), ld(bank)
+    g.batch, g.n_in, g.n_out, g.up, g.down, g.half = B, n_in, n_out, up, down, half
+    check(lib().tt2_resample(C.byref(g), stream_ptr()), "tt2_resample")
+    return y, out_lens
+
+
 def _drop_into(s, drop: Drop):
     s.drop_seed, s.drop_site, s.drop_thr, s.drop_scale = drop.fields()
 
