@@ -1077,23 +1077,52 @@ int tt2_comm_standin(const void* src, void* scratch, size_t bytes, double second
  * hop, so the batch's frames are one strided matrix (row r at sample r * hop, ld = hop) and
  * utterance b owns rows [b * R, b * R + n_frames_b), R = Lp / hop.  Replaces the reference
  * pipeline's librosa / torch.stft feature extraction and its vocoder hand-off. */
-/* padded[b][j] = x[b][reflect(j - pad)] for j < len_b + 2 pad (np.pad "reflect"), else 0;
- * lens may be NULL (all len); pad < len. */
+/* Every entry below returns TT2_E_INVALID, with its own name in tt2_last_error(), before any launch
+ * where a refusal is stated; nothing is written then.
+ *
+ * padded[b][j] = x[b][reflect(j - pad)] for j < len_b + 2 pad (np.pad "reflect"), else 0, for all
+ * j < padded_len; x [batch][ldx], padded [batch][padded_len].  lens may be NULL (all len).  Ragged
+ * rules: len_b = min(lens[b], len) (an entry above len counts as len); len_b <= 0 gives a row of
+ * zeros and reads nothing; 0 < len_b <= pad is NOT np.pad's repeated reflection: s = j - pad is
+ * reflected once about 0 (s < 0: -s), then once about len_b - 1 (s >= len_b: 2 (len_b - 1) - s),
+ * then clamped into [0, len_b).  Samples at and beyond len_b are never read.
+ * Refused: x or padded NULL; batch <= 0; len <= 0; pad < 0 or pad >= len;
+ * padded_len < len + 2 pad; ldx < len when batch > 1. */
 int tt2_reflect_pad(const float* x, int64_t ldx, const int32_t* lens, int32_t batch, int32_t len, float* padded,
                     int64_t padded_len, int32_t pad, hipStream_t stream);
-/* mag[r][k] = |spec[r][k] + i spec[r][n_bins + k]| (k < n_bins), zero padding to ld_mag. */
+/* mag[r][k] = |spec[r][k] + i spec[r][n_bins + k]| (k < n_bins), +0 in the padding columns
+ * [n_bins, ld_mag), for r < m.  Columns of spec at and beyond 2 n_bins are never read.
+ * Refused: spec or mag NULL; m <= 0; ld_spec < 2 n_bins; ld_mag < n_bins. */
 int tt2_spec_magnitude(const float* spec, int64_t ld_spec, int32_t m, int32_t n_bins, float* mag, int64_t ld_mag,
                        hipStream_t stream);
-/* out = mag * e / |e| as [re | im] rows (phase 0 where est is NULL or e == 0): Griffin-Lim's
- * projection onto the target magnitude. */
+/* out = mag * e / |e| as [re | im] rows, e = est[r][k] + i est[r][n_bins + k] (phase 0, that is
+ * re = mag and im = +0 * mag, where est is NULL or e == 0): Griffin-Lim's projection onto the target
+ * magnitude.  The padding columns [2 n_bins, ld_out) are set to +0; columns of mag at and beyond
+ * n_bins and of est at and beyond 2 n_bins are never read.
+ * Refused: mag or out NULL; m <= 0; ld_mag < n_bins; ld_out < 2 n_bins or ld_out > 3 n_bins;
+ * ld_est < 2 n_bins when est is given. */
 int tt2_spec_rephase(const float* mag, int64_t ld_mag, const float* est, int64_t ld_est, int32_t m, int32_t n_bins,
                      float* out, int64_t ld_out, hipStream_t stream);
-/* y[b][t] = sum_f frames[b * R + f][t + n_fft/2 - f hop] / sum_f hann^2(...) for t < len_b
- * (least-squares iSTFT overlap-add, centre padding removed), 0 beyond. */
+/* y[b][t] = sum_f frames[b * R + f][t + n_fft/2 - f hop] / sum_f hann^2(t + n_fft/2 - f hop) for
+ * t < len_b (least-squares iSTFT overlap-add, centre padding removed), over the frames
+ * f < 1 + len_b / hop that cover the sample, hann the periodic Hann window of n_fft points; 0 where
+ * the divisor is at most 1e-8, and 0 for len_b <= t < len.  R = rows_per_utt; y [batch][ld_y].
+ * len_b = min(lens[b], len), lens NULL: all len; len_b <= 0 gives a row of zeros.  Frame rows at and
+ * beyond 1 + len_b / hop of an utterance are never read.
+ * Refused: frames or y NULL; batch <= 0; len <= 0; hop <= 0; n_fft < hop; ld_frames < n_fft;
+ * rows_per_utt * hop < len + n_fft; ld_y < len when batch > 1. */
 int tt2_overlap_add(const float* frames, int64_t ld_frames, const int32_t* lens, int32_t batch, int32_t len,
                     int32_t rows_per_utt, int32_t n_fft, int32_t hop, float* y, int64_t ld_y, hipStream_t stream);
-/* scatter = 0: mel[b][t][c] = log(max(rows[b * R + t][c], clamp)) (t < frames_b, else log clamp);
- * scatter = 1: rows[b * R + t][c] = exp(mel[b][t][c]) (t < frames_b, else 0).  mel [batch][t][n_mels]. */
+/* scatter = 0: mel[b][t][c] = log(max(rows[b * R + t][c], clamp)) (t < frames_b, else log clamp),
+ * for every row below the argument t; rows is only read;
+ * scatter = 1: rows[b * R + t][c] = exp(mel[b][t][c]) (t < frames_b), +0 for every other row of the
+ * utterance, frames_b <= t < R; mel is only read.  mel [batch][t][n_mels], R = rows_per_utt, c < n_mels
+ * (columns [n_mels, ld_rows) of rows are neither read nor written).
+ * frames_b = min(frames[b], t) (an entry above t counts as t; frames NULL: all t); frames[b] <= 0
+ * makes the whole utterance silence (scatter = 0) or zero rows (scatter = 1).  Rows of the source at
+ * and beyond frames_b are never read.
+ * Refused: rows or mel NULL; batch <= 0; t <= 0; t > rows_per_utt; n_mels <= 0; ld_rows < n_mels;
+ * clamp not > 0. */
 int tt2_mel_rows(float* rows, int64_t ld_rows, float* mel, const int32_t* frames, int32_t batch, int32_t t,
                  int32_t n_mels, int32_t rows_per_utt, float clamp, int32_t scatter, hipStream_t stream);
 
