@@ -227,8 +227,10 @@ int tt2_attn_bwd(const tt2_attn_args* a, hipStream_t stream);
  * out + kappa * sum g:  dS = P (dP + kappa W - (delta + kappa g))  on those heads and rows, with
  * kappa read from device memory (coef; tt2_guided_attn_loss writes it).  o_out and lse of the guided
  * forward equal tt2_attn_fwd's bit for bit; the guided backward leaves delta + kappa g in the delta
- * scratch.  Causal launches are refused (TT2_E_INVALID).  Same variants and parts as the plain
- * calls. */
+ * scratch (kappa g counted on the guided heads' valid rows only; parts = 2 alone runs no dQ block
+ * and leaves the scratch untouched).  Same variants and parts as the plain calls.
+ * Refused (TT2_E_INVALID, nothing is launched or written): a NULL guide; causal != 0; rows NULL;
+ * coef NULL in the backward; sigma <= 0 or NaN; heads < 0 or heads > the attention's heads. */
 typedef struct tt2_attn_guide {
   const int32_t* q_len;   /* [batch] valid query rows (may be NULL: tq) */
   float* rows;            /* g, [batch*heads, tq] f32: written by fwd, read by bwd */
@@ -243,7 +245,13 @@ int tt2_attn_bwd_guided(const tt2_attn_args* a, const tt2_attn_guide* g, hipStre
  *   N     = n_layers * guide_heads * sum_b Tx_b * Ty_b   (from the device lengths)
  *   term  = scale * (sum of rows[l] over the guided heads) / N     (0 if N = 0)
  *   coef  = scale * grad_scale / N   (kappa for tt2_attn_bwd_guided; 0 if N = 0)
- *   loss_out[0] += term              (loss_out may be NULL) */
+ *   loss_out[0] += term              (loss_out may be NULL; untouched if N = 0)
+ * Lengths are cut to [0, tk] / [0, tq].  Each rows[l] holds whole [batch*heads, tq] rows and the
+ * guided heads' rows are summed whole (the forward leaves exactly 0 past Ty_b), the other heads'
+ * rows are not read.
+ * Refused (TT2_E_INVALID, nothing is launched or written): NULL args, term or coef; n_layers < 0 or
+ * n_layers > TT2_GUIDE_MAX_LAYERS; batch, tq or tk < 0; heads <= 0; guide_heads < 0 or guide_heads >
+ * heads; heads * tq above INT32_MAX; a NULL rows[l] with l < n_layers. */
 #define TT2_GUIDE_MAX_LAYERS 16
 typedef struct tt2_guide_loss_args {
   const float* rows[TT2_GUIDE_MAX_LAYERS];   /* the guided layers' g buffers, [batch*heads, tq] f32 each */
@@ -266,7 +274,14 @@ int tt2_guided_attn_loss(const tt2_guide_loss_args* a, hipStream_t stream);
  * tq).  Non-causal only: causal != 0 is refused (TT2_E_INVALID), as are scale <= 0 and
  * n_layers > TT2_GUIDE_MAX_LAYERS.  variant as in tt2_attn_args: 0 auto (bf16: the MFMA kernel,
  * whose scores are formed exactly as the v3 forward forms them; f32: the plain kernel), 1 the
- * plain kernel (one work group per row), 2 / 3 the MFMA kernel with 2 / 4 waves per work group. */
+ * plain kernel (one work group per row), 2 / 3 the MFMA kernel with 2 / 4 waves per work group.
+ * Refused (TT2_E_INVALID, nothing is launched or written): NULL args; head_dim != 64; causal != 0;
+ * n_layers < 0 or n_layers > TT2_GUIDE_MAX_LAYERS; a dtype other than bf16 or f32; batch, tq or tk
+ * < 0, heads <= 0, scale <= 0 or NaN, batch * heads above INT32_MAX; q_ld or k_ld that is no
+ * multiple of 16 bytes or is below heads * 64; NULL pmax or amax; a NULL q[l], k[l] or lse[l] with
+ * l < n_layers; for the MFMA kernel one batch element's q or k spanning more than 2 GiB
+ * ((tq * q_ld + 64) * 2 bytes above INT32_MAX, likewise tk * k_ld); for the plain kernel more than
+ * 65535 (batch, head) pairs. */
 typedef struct tt2_align_args {
   const void* q[TT2_GUIDE_MAX_LAYERS];      /* per layer: [batch*tq, >= heads*64], row stride q_ld */
   const void* k[TT2_GUIDE_MAX_LAYERS];      /* per layer: [batch*tk, >= heads*64], row stride k_ld */
@@ -290,7 +305,12 @@ int tt2_attn_align(const tt2_align_args* a, hipStream_t stream);
  *   sel_focus[b]    = focus of the chosen head
  *   durations[b][t] = #{n < Ty_b : amax of the chosen head at n == t}, t < tk   (int32)
  * durations[b][t] is exactly 0 for t >= key_len[b], and sum_t durations[b][t] = Ty_b whenever
- * utterance b has a visible key (else 0).  n_layers * heads <= 1024. */
+ * utterance b has a visible key (else 0).  An amax entry that is negative or at or past
+ * min(tk, key_len[b]) counts nowhere; pmax / amax rows n >= Ty_b are not read.
+ * Refused (TT2_E_INVALID, nothing is launched or written): NULL args; a NULL pmax, amax, focus,
+ * sel, sel_focus or durations; n_layers < 1 or n_layers > TT2_GUIDE_MAX_LAYERS; batch, tq or tk < 0,
+ * heads <= 0, n_layers * heads above 1024; a mode other than 0 or 1; in mode 1 a sel_layer outside
+ * [0, n_layers) or a sel_head outside [0, heads). */
 typedef struct tt2_align_dur_args {
   const float* pmax; const int32_t* amax;         /* [n_layers, batch*heads, tq] */
   const int32_t* key_len; const int32_t* q_len;   /* [batch], device (NULL: tk / tq) */

@@ -209,13 +209,18 @@ def selector_codes(Tk):
     return k
 
 
-def selector_problem(B, H, Tq, Tk, key_len, causal, pair_frac=0.5, seed=0):
+def selector_problem(B, H, Tq, Tk, key_len, causal, pair_frac=0.5, seed=0, diag=None):
     """The exact problem.  Each query row copies the code of one visible key (Q = K[t1]) or of two
     that share the first code (Q = K[t1] + K[t2], t2 = t1 mod 32): the best match leads every other
     key by 4096 in the dot product, 4096 * 0.125 * log2(e) = 738 in the log2 domain, so every other
     probability is exactly 0 in float32 (and below 1e-221 in float64).  P is 1, or 1/2 twice;
     O = V[t1] or (V[t1] + V[t2]) / 2; dS = 0 on the one-hot rows and +-(dP1 - dP2) / 4 on the pair
-    rows; every partial sum is a small dyadic number.  A row with no visible key gets Q = 0."""
+    rows; every partial sum is a small dyadic number.  A row with no visible key gets Q = 0.
+
+    diag = (q_len, share) (non-causal; default None changes nothing): a row n < Ty_b that has a key
+    on the guided-attention diagonal, t Ty_b == n Tx_b (Tx_b the visible keys, Ty_b = q_len[b] cut
+    to [0, Tq]), takes that key as t1 with probability `share`; t2 is then off the diagonal, so a
+    pair row mixes an on-diagonal key with an off-diagonal one (tests/_align_refs.py)."""
     g = torch.Generator().manual_seed(3000 * seed + 7 * Tq + Tk)
     codes = selector_codes(Tk)
     p0 = Problem(torch.zeros(B, H, Tq, D, dtype=F64), codes.expand(B, H, Tk, D).clone(),
@@ -223,6 +228,14 @@ def selector_problem(B, H, Tq, Tk, key_len, causal, pair_frac=0.5, seed=0):
     nvis = visible_counts(p0)[:, None, :].expand(B, H, Tq)                  # keys 0 .. nvis - 1 are visible
     u = torch.rand(3, B, H, Tq, generator=g, dtype=F64)
     t1 = (u[0] * nvis).long().clamp(max=(nvis - 1).clamp_min(0))
+    if diag is not None:
+        assert not causal
+        q_len, share = diag
+        ty = (torch.full((B,), Tq) if q_len is None else torch.tensor(q_len).clamp(0, Tq))[:, None, None]
+        n = torch.arange(Tq)[None, None, :]
+        td = (n * nvis) // ty.clamp_min(1)
+        on = (n < ty) & (nvis > 0) & (td * ty == n * nvis) & (torch.rand(B, H, Tq, generator=g, dtype=F64) < share)
+        t1 = torch.where(on, td, t1)
     res = t1 % 32
     cnt = (nvis - res + 31) // 32                                           # visible keys = t1 mod 32
     i2 = (t1 // 32 + 1 + (u[1] * (cnt - 1)).long().clamp(max=(cnt - 2).clamp_min(0))) % cnt.clamp_min(1)

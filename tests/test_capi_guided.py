@@ -63,3 +63,70 @@ def test_guided_struct_layout_matches_c(lib, tmp_path):
             assert getattr(structs[name], field).offset == int(val), (name, field)
         seen += 1
     assert seen == 1 + sum(1 + len(c._fields_) for c in structs.values())
+
+
+# ------------------------------------------------------------------ refusals (no launch: host buffers)
+def _fill(struct, fields, buf):
+    """A struct from keyword -> value; "buffer" stands for a non-null host pointer."""
+    s = struct()
+    for k, v in fields.items():
+        if isinstance(v, (list, tuple)):
+            for i, x in enumerate(v):
+                getattr(s, k)[i] = ctypes.addressof(buf) if x == "buffer" else x
+        else:
+            setattr(s, k, ctypes.addressof(buf) if v == "buffer" else v)
+    return s
+
+
+P = "buffer"
+ATTN_VALID = dict(q=P, k=P, v=P, o=P, dout=P, o_out=P, dq=P, dk=P, dv=P, lse=P, delta=P, q_ld=192, k_ld=192, v_ld=192,
+                  o_ld=192, do_ld=192, dq_ld=192, dk_ld=192, dv_ld=192, key_len=None, batch=2, heads=3, head_dim=64,
+                  tq=33, tk=64, causal=0, dtype=1, scale=0.125, variant=0, parts=0)
+GUIDE_VALID = dict(q_len=None, rows=P, coef=P, sigma=0.4, heads=2)
+# check_guide's four refusals: (changes of the attention args, changes of the guide or None for no guide)
+GUIDE_REFUSALS = [({}, None), (dict(causal=1), {}), ({}, dict(rows=None)), ({}, dict(sigma=0.0)), ({}, dict(sigma=-0.4)),
+                  ({}, dict(sigma=float("nan"))), ({}, dict(heads=-1)), ({}, dict(heads=4))]
+LOSS_VALID = dict(rows=[P, P], key_len=None, q_len=None, loss_out=None, term=P, coef=P, n_layers=2, batch=2, heads=3,
+                  guide_heads=2, tq=33, tk=64, scale=10.0, grad_scale=1.0)
+LOSS_REFUSALS = [dict(term=None), dict(coef=None),                                   # "term / coef"
+                 dict(n_layers=17), dict(n_layers=-1),                               # "too many layers"
+                 dict(batch=-1), dict(tq=-1), dict(tk=-1), dict(heads=0), dict(guide_heads=-1), dict(guide_heads=4),
+                 dict(heads=3, guide_heads=0, tq=2 ** 30),                           # "shape": heads * tq in 32 bits
+                 dict(rows=[P, None]), dict(rows=[None, P])]                         # "rows buffer missing"
+
+
+def test_every_stated_refusal(lib):
+    """Valid arguments plus one bad field per row: TT2_E_INVALID with the entry's name in
+    tt2_last_error(), before any launch (the buffers are host memory)."""
+    L = lib.load()
+    buf = (ctypes.c_char * 4096)()
+    E = lib.E_INVALID
+
+    def refused(name, *args):
+        assert L.tt2_dtw(None, None) == E and b"tt2_dtw" in L.tt2_last_error()     # so the message is this call's
+        assert getattr(L, name)(*args, None) == E, (name, args)
+        assert name.encode() in L.tt2_last_error(), (name, L.tt2_last_error())
+
+    for name in ("tt2_attn_fwd_guided", "tt2_attn_bwd_guided"):
+        cases = GUIDE_REFUSALS + ([({}, dict(coef=None))] if "bwd" in name else [])
+        for akw, gkw in cases:
+            a = _fill(lib.AttnArgs, dict(ATTN_VALID, **akw), buf)
+            g = None if gkw is None else ctypes.byref(_fill(lib.AttnGuide, dict(GUIDE_VALID, **gkw), buf))
+            refused(name, ctypes.byref(a), g)
+    refused("tt2_guided_attn_loss", None)
+    for kw in LOSS_REFUSALS:
+        assert set(kw) <= set(LOSS_VALID)
+        refused("tt2_guided_attn_loss", ctypes.byref(_fill(lib.GuideLossArgs, dict(LOSS_VALID, **kw), buf)))
+
+
+def test_header_states_the_refusals():
+    header = open(os.path.join(ROOT, "include", "tt2_capi.h")).read()
+    sec = header[header.index("Guided attention (diagonal loss"):header.index("Alignment statistics of forwards")]
+    sec = " ".join(sec.replace("*", " ").split())
+    for phrase in ("a NULL guide", "causal != 0", "rows NULL", "coef NULL in the backward", "sigma <= 0 or NaN",
+                   "heads < 0 or heads > the attention's heads", "NULL args, term or coef",
+                   "n_layers < 0 or n_layers > TT2_GUIDE_MAX_LAYERS", "batch, tq or tk < 0", "heads <= 0",
+                   "guide_heads < 0 or guide_heads > heads", "heads tq above INT32_MAX", "a NULL rows[l] with l < n_layers",
+                   "parts = 2 alone runs no dQ block and leaves the scratch untouched"):
+        assert phrase in sec, phrase
+    assert sec.count("Refused (TT2_E_INVALID") == 2

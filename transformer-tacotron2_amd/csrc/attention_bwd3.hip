@@ -365,12 +365,15 @@ __global__ __launch_bounds__(NW * 64) void attn_bwd_dkdv3_kernel(ArgsT<G> a) {
 // beside the dQ workgroups instead of after them on a mostly idle chip
 // (G: held to two waves per SIMD, the plain kernel's occupancy, without scratch; its natural
 // allocation is 260 registers.  Measured 47.3 us held against 48.7 not held)
+// G: the dQ blocks publish delta + kappa g although no block of this launch reads it, because
+// tt2_capi.h promises it in the delta scratch after every guided backward (one store per row,
+// before the tile loop); the plain launch leaves the scratch alone, as before.
 template <int NW, bool G>
 __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(G ? 2 : 1)))
 void attn_bwd_fused3_kernel(ArgsT<G> a, int nkb) {
   __shared__ __attribute__((aligned(16))) char smem[G ? ATTN_BWD3_SMEM_G : ATTN_BWD3_SMEM];
   if ((int)blockIdx.y < nkb) attn_bwd_dkdv3_body<NW, G>(a, blockIdx.x, blockIdx.y, smem, true);
-  else attn_bwd_dq3_body<NW, G>(a, blockIdx.x, (int)blockIdx.y - nkb, (int)gridDim.y - nkb, smem, false);
+  else attn_bwd_dq3_body<NW, G>(a, blockIdx.x, (int)blockIdx.y - nkb, (int)gridDim.y - nkb, smem, G);
 }
 
 }  // namespace
