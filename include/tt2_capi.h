@@ -546,6 +546,58 @@ typedef struct tt2_resample_args {
 } tt2_resample_args;
 int tt2_resample(const tt2_resample_args* a, hipStream_t stream);
 
+/* Leading and trailing silence trimming of a batch of utterances, on frame energies relative to the
+ * utterance's loudest frame (librosa.effects.trim's rule with ref = np.max): three launches, no host
+ * synchronisation.  For utterance b, len_b = clamp(lens[b], 0, n_in) (lens NULL: n_in).  The frame
+ * length is frame = 2 * r * hop; F_b = 0 when len_b = 0, otherwise F_b = 1 + len_b / hop (integer
+ * division).  Frame f covers the samples [f * hop - r * hop, f * hop + r * hop) within [0, len_b):
+ * centred, zero-padded frames, the grid of librosa.feature.rms(center=True, pad_mode="constant").
+ * Samples outside the utterance count as 0 and are not read.
+ *   Frame energy.  e[b][f] is the f32 sum of x^2 over the frame, taken through blocks: block j is
+ * the samples [j * hop, (j + 1) * hop) within [0, len_b), n of them.  Sample i of a block belongs to
+ * lane (i / 4) mod 64; a lane adds its squares (each rounded to f32) to one accumulator from +0 with
+ * i ascending, and the 64 accumulators are added in one fixed tree.  The order depends on hop and n
+ * alone, never on batch, on the utterance's position, on n_in or on the row's alignment.  e[b][f] is
+ * the sum, from +0 in ascending block order, of the sums of blocks f - r .. f + r - 1; blocks outside
+ * [0, ceil(len_b / hop)) contribute +0.  Where every square and partial sum is exactly representable
+ * in f32, every bit is thereby defined.
+ *   Decision.  emax_b = max over f < F_b of e[b][f].  Frame f is loud iff e[b][f] > ratio * emax_b
+ * (one f32 multiply, a strict compare): an all-zero utterance has no loud frame, and a frame exactly
+ * on the threshold is silent.  With f0 the lowest and f1 the highest loud frame,
+ *   start_b = max(0, f0 * hop - keep),  end_b = min(len_b, (f1 + 1) * hop + keep)
+ * in 64-bit arithmetic; with no loud frame start_b = end_b = 0.  Interior silence is kept.
+ *   Outputs.  out_b = min(end_b - start_b, n_out); y[b][i] = x[b][start_b + i] for i < out_b (the
+ * sample's bits, copied) and exactly +0 for out_b <= i < n_out; nothing is written at or past column
+ * n_out of a row.  out_lens[b] = out_b and start[b] = start_b where those pointers are given;
+ * energy[b][f] = e[b][f] for f < F_b and 0 for F_b <= f < n_in / hop + 1 when energy is given.  No
+ * sample at an index >= len_b is read.  A non-finite sample leaves that utterance's outputs
+ * unspecified; even then nothing is read or written out of bounds,
+ * 0 <= start <= start + out_b <= len_b holds, and other utterances are unaffected.  Results are
+ * bit-identical run to run (no floating-point atomics).
+ *   `workspace` (16-B aligned) of tt2_trim_workspace_size(batch, n_in, hop) bytes holds the block
+ * sums and each utterance's (start, out).
+ *   Refused with TT2_E_INVALID before any launch: hop < 1; r < 1 or r > TT2_TRIM_MAX_R; 2 * r * hop
+ * beyond int32; keep < 0; ratio not finite, < 0 or > 1; batch, n_in or n_out negative; x_ld < n_in or
+ * y_ld < n_out; energy given with energy_ld < n_in / hop + 1; a null y; a null x with samples to read
+ * (batch, n_out and n_in all positive); a workspace below the size query; more than 2^31 - 1 work
+ * groups.  batch = 0 or n_out = 0 succeeds without a launch (out_lens, start and energy are then not
+ * written); n_in = 0 with n_out > 0 launches, zero-fills and writes out_lens = start = 0. */
+#define TT2_TRIM_MAX_R 16   /* frame = 2 * r * hop */
+typedef struct tt2_trim_args {
+  const float* x;          /* [batch, x_ld] */
+  const int32_t* lens;     /* [batch] valid input samples, device, or NULL (= n_in) */
+  float* y;                /* [batch, y_ld] */
+  int32_t* out_lens;       /* optional [batch] */
+  int32_t* start;          /* optional [batch] */
+  float* energy;           /* optional [batch, energy_ld] */
+  void* workspace; size_t workspace_bytes;
+  int64_t x_ld, y_ld, energy_ld;
+  int32_t batch, n_in, n_out, hop, r, keep;
+  float ratio;
+} tt2_trim_args;
+size_t tt2_trim_workspace_size(int batch, int n_in, int hop);
+int tt2_trim(const tt2_trim_args* a, hipStream_t stream);
+
 /* ------------------------------------------------------------------ decode
  * One query row per batch element (the AR decode step):
  * out[b*o_ld + 64h ..] = softmax(scale q k^T) v over keys j < n_b of batch b,

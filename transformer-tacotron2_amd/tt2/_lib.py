@@ -306,6 +306,26 @@ SIGNATURES.update({
 })
 
 
+TRIM_MAX_R = 16   # TT2_TRIM_MAX_R: frame = 2 * r * hop
+
+
+class TrimArgs(C.Structure):
+    """tt2_trim_args: leading / trailing silence trimming of a batch of utterances."""
+    _fields_ = [
+        ("x", vp), ("lens", vp), ("y", vp), ("out_lens", vp), ("start", vp), ("energy", vp),
+        ("workspace", vp), ("workspace_bytes", sz),
+        ("x_ld", i64), ("y_ld", i64), ("energy_ld", i64),
+        ("batch", i32), ("n_in", i32), ("n_out", i32), ("hop", i32), ("r", i32), ("keep", i32),
+        ("ratio", f32),
+    ]
+
+
+SIGNATURES.update({
+    "tt2_trim_workspace_size": ([C.c_int, C.c_int, C.c_int], C.c_size_t),
+    "tt2_trim": ([C.POINTER(TrimArgs), vp], C.c_int),
+})
+
+
 class ReduceArgs(C.Structure):
     _fields_ = [("src", vp), ("dst", vp), ("ld", i64), ("rows", i32), ("cols", i32), ("beta", f32)]
 

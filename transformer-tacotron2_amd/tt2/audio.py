@@ -16,6 +16,9 @@
   rate) by a polyphase Kaiser-windowed sinc bank designed in float64 on the host (tt2_resample, one
   launch per batch): the step in front of everything above for corpora that ship at 24, 44.1 or
   48 kHz.
+* ``SilenceTrimmer``: leading and trailing silence off a batch, by frame energy relative to the
+  utterance's loudest frame (tt2_trim; librosa.effects.trim's rule), optionally behind a Resampler:
+  the step that VCTK-like corpora need before alignments and stop tokens can be learnt.
 
 Every transform runs on the GPU through libtt2: the window-folded DFT basis, its
 inverse and the mel filterbank are f32 ``tt2_gemm`` operands (constant tables built
@@ -412,6 +415,87 @@ class Resampler:
         out_lens = torch.empty(B, dtype=torch.int32, device=self.dev)
         ops.resample(audio, y, self.taps(), self.up, self.down, self.half, lens=lens32, out_lens=out_lens)
         return y, out_lens
+
+
+class Trimmed(NamedTuple):
+    """SilenceTrimmer.trim(): audio [B, L] f32 (zeros past lens), lens [B] int32 samples kept, start [B]
+    int32 first kept sample of the input, energy [B, L // hop + 1] f32 frame energies or None."""
+    audio: torch.Tensor
+    lens: torch.Tensor
+    start: torch.Tensor
+    energy: torch.Tensor | None
+
+
+class SilenceTrimmer:
+    """Leading / trailing silence trimming of a padded batch (tt2_trim; include/tt2_capi.h has the
+    definition): everything before the first and after the last frame whose energy is within top_db
+    of the utterance's loudest frame goes, `keep` samples either side stay, interior silence stays.
+    With keep = 0 this is librosa.effects.trim's rule with ref = np.max, and the defaults (60 dB,
+    frames of 2048 at hop 512) are librosa's: they were chosen without a speech corpus, and
+    validating top_db on VCTK or LibriTTS is open.  `frame` must be an even multiple of `hop`, at
+    most 2 * TT2_TRIM_MAX_R hops.  With resampler=rs (a Resampler whose sr_out is `sr`) a call runs rs
+    first and trims its output, so that one object takes a corpus from its own rate to trimmed
+    22.05 kHz audio wherever a resampler is accepted (data.collate, data.resample_corpus,
+    data.trim_corpus)."""
+
+    def __init__(self, top_db: float = 60.0, frame: int = 2048, hop: int = 512, keep: int = 0, sr: int = SR,
+                 resampler=None, device="cuda"):
+        from ._lib import TRIM_MAX_R
+        top_db = float(top_db)
+        if not (math.isfinite(top_db) and top_db >= 0.0):
+            raise ValueError(f"SilenceTrimmer: top_db must be finite and not negative, got {top_db}")
+        if int(frame) != frame or int(hop) != hop or hop < 1 or frame < 2 * hop or frame % (2 * hop) \
+                or frame // (2 * hop) > TRIM_MAX_R:
+            raise ValueError(f"SilenceTrimmer: frame must be 2 * r * hop with 1 <= r <= TT2_TRIM_MAX_R = {TRIM_MAX_R}, "
+                             f"got frame {frame}, hop {hop}")
+        if int(keep) != keep or keep < 0:
+            raise ValueError(f"SilenceTrimmer: keep must be an integer >= 0, got {keep}")
+        if resampler is not None and int(resampler.sr_out) != int(sr):
+            raise ValueError(f"SilenceTrimmer: the resampler writes {resampler.sr_out} Hz, the trimmer works at {sr} Hz")
+        self.top_db, self.frame, self.hop, self.keep, self.sr = top_db, int(frame), int(hop), int(keep), int(sr)
+        self.r = self.frame // (2 * self.hop)
+        # the power ratio in float64, rounded once to f32 (the C argument is an f32)
+        self.ratio = float(torch.tensor(10.0 ** (-top_db / 10.0), dtype=torch.float64).float())
+        self.resampler = resampler
+        self.dev = torch.device(device)
+        self._ws = ops.Workspace()
+
+    sr_in = property(lambda self: self.resampler.sr_in if self.resampler is not None else self.sr)
+    sr_out = property(lambda self: self.sr)
+
+    def params(self) -> dict:
+        p = {"top_db": self.top_db, "frame": self.frame, "hop": self.hop, "r": self.r, "keep": self.keep,
+             "ratio": self.ratio, "sr": self.sr}
+        if self.resampler is not None:
+            p["resampler"] = self.resampler.params()
+        return p
+
+    def trim(self, audio: torch.Tensor, lens: torch.Tensor | None = None, want_energy: bool = False) -> Trimmed:
+        """audio [B, L] f32 at sr_in, lens [B] samples (optional) -> Trimmed, every field a fresh
+        tensor; the scratch is this object's own, grown on demand.  On the current stream, no host
+        synchronisation."""
+        if self.resampler is not None:
+            audio, lens = self.resampler(audio, lens)
+        audio = audio.to(self.dev, torch.float32)
+        B, L = audio.shape
+        if audio.stride(1) != 1 and L > 1:
+            audio = audio.contiguous()
+        lens32 = lens.to(self.dev, torch.int32).contiguous() if lens is not None else None
+        energy = torch.zeros(B, L // self.hop + 1, dtype=torch.float32, device=self.dev) if want_energy else None
+        if B == 0 or L == 0:
+            z = torch.zeros(B, dtype=torch.int32, device=self.dev)
+            return Trimmed(torch.zeros(B, L, dtype=torch.float32, device=self.dev), z, z.clone(), energy)
+        y = torch.empty(B, L, dtype=torch.float32, device=self.dev)
+        out_lens = torch.empty(B, dtype=torch.int32, device=self.dev)
+        start = torch.empty(B, dtype=torch.int32, device=self.dev)
+        ops.trim(audio, y, self.hop, self.r, self.keep, self.ratio, lens=lens32, out_lens=out_lens, start=start,
+                 energy=energy, workspace=self._ws)
+        return Trimmed(y, out_lens, start, energy)
+
+    def __call__(self, audio: torch.Tensor, lens: torch.Tensor | None = None):
+        """(audio_out [B, L] f32, out_lens [B] int32): the resampler protocol."""
+        t = self.trim(audio, lens)
+        return t.audio, t.lens
 
 
 def phoneme_average(values: torch.Tensor, durations: torch.Tensor, mask: torch.Tensor | None = None) -> torch.Tensor:

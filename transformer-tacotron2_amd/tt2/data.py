@@ -20,6 +20,9 @@
   not at the rate it is asked for; ``resample_corpus`` (``tools/resample_corpus.py``) rewrites a
   corpus at 22.05 kHz through ``tt2.audio.Resampler``, and ``collate`` can run the same resampler on
   the fly.  Everything downstream (mels, pitch, durations, MCD) stays at 22.05 kHz.
+* ``trim_corpus`` (``tools/trim_corpus.py``): the corpus with leading and trailing silence removed by
+  ``tt2.audio.SilenceTrimmer`` (which can resample in the same pass), with a ``trim.json`` manifest;
+  a SilenceTrimmer also fits ``collate(..., resampler=)`` as it is.
 """
 from __future__ import annotations
 
@@ -333,5 +336,69 @@ def resample_corpus(ds: LJSpeech, out_root: str, resampler, batch_size: int = 16
                                                 "clipped": clipped}
     shutil.copyfile(os.path.join(ds.root, "metadata.csv"), os.path.join(out_root, "metadata.csv"))
     with open(os.path.join(out_root, "resample.json"), "w") as f:
+        json.dump(manifest, f, indent=1, sort_keys=True)
+    return manifest
+
+
+def trim_corpus(ds: LJSpeech, out_root: str, trimmer, batch_size: int = 16):
+    """The corpus `ds` with leading and trailing silence removed, as a corpus of the same layout
+    under out_root: out_root/wavs/<id>.wav (PCM16 mono at the trimmer's sr_out: rint(x * 32768)
+    clipped to [-32768, 32767]), a copy of metadata.csv, and out_root/trim.json: {"trimmer": its
+    params(), "utterances": {id: {"samples_in", "start", "samples_out", "clipped"}},
+    "removed_seconds": samples_in / sr_in - samples_out / sr_out summed over the corpus,
+    "empty": [ids]}.  `start` and `samples_out` count samples at sr_out (after the trimmer's
+    resampler, when it has one).  An utterance trimmed to nothing is not written: it is listed under
+    "empty" and its line is left out of the copied metadata.csv, so that nothing downstream meets a
+    zero-length file.  `trimmer` is a tt2.audio.SilenceTrimmer whose sr_in is ds.sr, or any object
+    with sr_in, sr_out, params() and trim(audio [B, L], lens [B]) -> (audio, lens, start, energy):
+    one call per batch of batch_size utterances in corpus order.  Returns the manifest."""
+    import shutil
+    from scipy.io import wavfile
+    if int(trimmer.sr_in) != int(getattr(ds, "sr", 22050)):
+        raise ValueError(f"trim_corpus: the trimmer reads {trimmer.sr_in} Hz, the corpus is at "
+                         f"{getattr(ds, 'sr', 22050)} Hz")
+    if batch_size < 1:
+        raise ValueError("trim_corpus: batch_size must be at least 1")
+    if os.path.abspath(out_root) == os.path.abspath(ds.root):
+        raise ValueError("trim_corpus: out_root is the corpus itself")
+    os.makedirs(os.path.join(out_root, "wavs"), exist_ok=True)
+    dev = getattr(trimmer, "dev", "cpu")
+    sr_in, sr_out = int(trimmer.sr_in), int(trimmer.sr_out)
+    manifest = {"trimmer": trimmer.params() if hasattr(trimmer, "params") else {}, "utterances": {}, "empty": []}
+    removed = 0.0
+    for s in range(0, len(ds), batch_size):
+        idx = list(range(s, min(s + batch_size, len(ds))))
+        wavs = [ds.wav(i) for i in idx]
+        audio = torch.zeros(len(idx), max(len(w) for w in wavs), dtype=torch.float32)
+        for b, w in enumerate(wavs):
+            audio[b, :len(w)] = torch.from_numpy(w)
+        lens = torch.tensor([len(w) for w in wavs], dtype=torch.int32)
+        y, out_lens, start = trimmer.trim(audio.to(dev), lens.to(dev))[:3]
+        y = torch.as_tensor(y).detach().float().cpu().numpy()
+        out_lens = [int(n) for n in torch.as_tensor(out_lens).cpu()]
+        start = [int(n) for n in torch.as_tensor(start).cpu()]
+        for b, i in enumerate(idx):
+            uid = str(ds.items[i][0])
+            q = np.rint(y[b, :out_lens[b]].astype(np.float64) * 32768.0)
+            clipped = int(((q < -32768) | (q > 32767)).sum())
+            manifest["utterances"][uid] = {"samples_in": len(wavs[b]), "start": start[b],
+                                           "samples_out": out_lens[b], "clipped": clipped}
+            removed += len(wavs[b]) / sr_in - out_lens[b] / sr_out
+            if out_lens[b] == 0:
+                manifest["empty"].append(uid)
+                continue
+            wavfile.write(os.path.join(out_root, "wavs", uid + ".wav"), sr_out,
+                          np.clip(q, -32768, 32767).astype(np.int16))
+    manifest["removed_seconds"] = removed
+    src, dst = os.path.join(ds.root, "metadata.csv"), os.path.join(out_root, "metadata.csv")
+    if not manifest["empty"]:
+        shutil.copyfile(src, dst)
+    else:
+        gone = set(manifest["empty"])
+        with open(src, encoding="utf-8", newline="") as f, open(dst, "w", encoding="utf-8", newline="") as g:
+            for line in f:
+                if line.split("|", 1)[0].rstrip("\r\n") not in gone:
+                    g.write(line)
+    with open(os.path.join(out_root, "trim.json"), "w") as f:
         json.dump(manifest, f, indent=1, sort_keys=True)
     return manifest

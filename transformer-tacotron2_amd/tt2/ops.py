@@ -755,6 +755,63 @@ def resample(x, y, bank, up, down, half, lens=None, out_lens=None):
     return y, out_lens
 
 
+def trim(x, y, hop, r, keep, ratio, lens=None, out_lens=None, start=None, energy=None, workspace=None):
+    """Leading / trailing silence trimming (tt2_trim_args): x [B, n_in] f32 -> y [B, n_out] f32, with
+    y[b, i] = x[b, start_b + i] for i < out_b and 0 after, where [start_b, end_b) runs from `keep`
+    samples before the first to `keep` samples after the last frame (length 2 * r * hop, hop `hop`,
+    centred, zero-padded) whose energy exceeds ratio times the utterance's loudest frame's.  x and y
+    are 2-D with a contiguous last dim (row views are fine).  lens [B] int32 bounds the valid samples
+    (None: n_in); out_lens [B] int32 and start [B] int32, when given, receive min(end_b - start_b,
+    n_out) and start_b; energy [B, >= n_in // hop + 1] f32, when given, the frame energies.
+    workspace: a Workspace (default: the module's).  On the current stream, no host
+    synchronisation.  Deterministic."""
+    who = "trim"
+    hop, r, keep, ratio = int(hop), int(r), int(keep), float(ratio)
+    if hop < 1 or not (1 <= r <= _lib.TRIM_MAX_R) or 2 * r * hop > 2 ** 31 - 1:
+        raise _lib.TT2Error(f"{who}: hop >= 1, 1 <= r <= {_lib.TRIM_MAX_R} and 2 * r * hop within int32, got {hop}, {r}")
+    if keep < 0 or not (0.0 <= ratio <= 1.0):
+        raise _lib.TT2Error(f"{who}: keep >= 0 and 0 <= ratio <= 1, got {keep}, {ratio}")
+    views = [("x", x), ("y", y)] + ([("energy", energy)] if energy is not None else [])
+    for name, t in views:
+        if t.dtype != torch.float32 or t.dim() != 2 or (t.shape[1] > 1 and t.stride(1) != 1):
+            raise _lib.TT2Error(f"{who}: {name} must be f32 [rows, cols] with a contiguous last dim")
+        if t.shape[0] != y.shape[0]:
+            raise _lib.TT2Error(f"{who}: {name} has {t.shape[0]} rows, y {y.shape[0]}")
+    B, n_in = x.shape
+    n_out = y.shape[1]
+    if energy is not None and energy.shape[1] < n_in // hop + 1:
+        raise _lib.TT2Error(f"{who}: energy needs {n_in // hop + 1} columns, got {energy.shape[1]}")
+
+    def ld(t):   # a single row's stride is arbitrary: any value that covers the row
+        return t.stride(0) if t.shape[0] > 1 else max(t.stride(0), t.shape[1])
+
+    for name, t in views:
+        if ld(t) < t.shape[1]:
+            raise _lib.TT2Error(f"{who}: {name}'s rows overlap (stride {t.stride(0)} below {t.shape[1]} columns)")
+    tensors = [t for _, t in views]
+    for name, t in (("lens", lens), ("out_lens", out_lens), ("start", start)):
+        if t is not None:
+            _need(f"{who}: {name}", t, B, torch.int32)
+            if not t.is_contiguous():
+                raise _lib.TT2Error(f"{who}: {name} must be contiguous")
+            tensors.append(t)
+    for t in tensors:
+        if t.device != y.device or not t.is_cuda:
+            raise _lib.TT2Error(f"{who}: every tensor must be on y's GPU")
+    g = _lib.TrimArgs()
+    g.x, g.lens, g.y = x.data_ptr(), ptr(lens), y.data_ptr()
+    g.out_lens, g.start, g.energy = ptr(out_lens), ptr(start), ptr(energy)
+    g.x_ld, g.y_ld, g.energy_ld = ld(x), ld(y), (ld(energy) if energy is not None else 0)
+    g.batch, g.n_in, g.n_out, g.hop, g.r, g.keep, g.ratio = B, n_in, n_out, hop, r, keep, ratio
+    L = lib()
+    need = L.tt2_trim_workspace_size(B, n_in, hop)
+    if need:
+        buf = (workspace or _WS).get(need)
+        g.workspace, g.workspace_bytes = buf.data_ptr(), buf.numel()
+    check(L.tt2_trim(C.byref(g), stream_ptr()), "tt2_trim")
+    return y, out_lens, start, energy
+
+
 def _drop_into(s, drop: Drop):
     s.drop_seed, s.drop_site, s.drop_thr, s.drop_scale = drop.fields()
 
