@@ -598,6 +598,80 @@ typedef struct tt2_trim_args {
 size_t tt2_trim_workspace_size(int batch, int n_in, int hop);
 int tt2_trim(const tt2_trim_args* a, hipStream_t stream);
 
+/* Integrated loudness of a batch of utterances by the gating of ITU-R BS.1770-4 over a two-section
+ * weighting filter, and a gain to a target level under a peak ceiling: five launches, no host
+ * synchronisation.  For utterance b, len_b = clamp(lens[b], 0, n_in) (lens NULL: n_in); samples at or
+ * past len_b are never read.  All arithmetic is IEEE float64 unless it says f32: at the K-weighting's
+ * pole radius of 0.989 (22.05 kHz) f32 carries do not survive a chunked evaluation.
+ *   Filter.  coef holds b0 b1 b2 a1 a2 of section 1, then of section 2 (a0 = 1); section 2 reads
+ * section 1's output.  Each is y[n] = b0 x[n] + b1 x[n-1] + b2 x[n-2] - a1 y[n-1] - a2 y[n-2] from zero
+ * state at n = 0.  It is evaluated in transposed direct form II, per sample and with fma(a, b, c) one
+ * rounding:
+ *   y1 = fma(b0, x, z1);  z1' = fma(b1, x, fma(-a1, y1, z2));  z2' = fma(-a2, y1, b2 * x)
+ * and the same for section 2 on y1 with state (w1, w2).  One sample advances s = (z1, z2, w1, w2) by
+ * s' = A s + B x, so the utterance is cut into chunks of 16 samples (chunk c holds samples 16 c ..
+ * 16 c + 15) and segments of 64 chunks: every chunk is run from zero state, the end states e are
+ * combined over a segment by an inclusive Kogge-Stone scan, at distance d = 1, 2, .. 32 chunk c with
+ * c mod 64 >= d taking e_c <- M_d e_(c-d) + e_c, M_d = A^(16 d), each row of the product
+ * fma(m3, v3, fma(m2, v2, fma(m1, v1, fma(m0, v0, e)))); the segments' end states are combined by the
+ * same scan with A^(1024 d), 64 segments a round, the first of a round taking the state that enters
+ * the round; then the scan over a segment's chunks is repeated with the segment's first chunk run
+ * from the segment's entry state, which gives every chunk's exact entry state, and every chunk is run
+ * from it.  The powers of A come from coef alone: A by its entries (-a1, 1; -a2, 0 for a section,
+ * b1' - a1' b0' and b2' - a2' b0' of section 2 under z1), then repeated squaring with each element a
+ * sum of four products in ascending index order.  The order depends on len_b and coef alone, never
+ * on batch, on the utterance's position, on n_in, x_ld or the row's alignment.
+ *   Energy.  sub[b][j] is the sum of y^2 (each square rounded) over the samples [j * step,
+ * (j + 1) * step), for j < S_b = len_b / step (integer division; a partial last sub-block is not
+ * used).  It is the sum, from +0 in ascending segment order, of one piece per segment that the
+ * sub-block touches; a piece's sample i (counted from the piece's first) belongs to lane i mod 64, a
+ * lane adds its own from +0 with i ascending, and the 64 lanes are added in one fixed xor tree.
+ * Block j < N_b = max(0, S_b - 3) has the sum E_j = ((sub[j] + sub[j+1]) + sub[j+2]) + sub[j+3].
+ *   Gates.  Block j passes the absolute gate iff E_j > abs_sum (strict).  G1 = (the sum of the passing
+ * E_j from +0, j ascending) / their count.  Block j passes both gates iff it passes the absolute gate
+ * and E_j > rel_ratio * G1 (one multiply, strict); G2 is the mean of those, formed the same way, and
+ * ms_b = G2 / (4 * step).  When no block passes (N_b = 0, silence, everything gated) the utterance is
+ * unmeasured.  A block exactly on a threshold fails it.
+ *   Results.  loud_b = f32(-0.691 + 10 * log10(ms_b)), -inf when unmeasured.  peak_b = max |x| over
+ * the valid samples, exact, 0 for len_b = 0.  g_b = f32(min(sqrt(target_ms / ms_b), ceiling /
+ * peak_b)), the ceiling term absent when peak_b = 0; limited_b = 1 iff the ceiling term is strictly
+ * the smaller.  Unmeasured: g_b = 1, limited_b = 0.  (The two f32 roundings, of g_b and of g_b * x, can
+ * carry the largest sample one f32 ulp past ceiling.)
+ *   Outputs.  y[b][i] = g_b * x[b][i] (one f32 multiply; for g_b = 1 the sample's own bits) for
+ * i < min(len_b, n_out) and exactly +0 for the remaining columns below n_out; nothing is written at
+ * or past column n_out.  y NULL measures only.  loud, gain, peak [batch] f32 and limited [batch]
+ * int32 are written where given.  energy[b][j] = f32(sub[b][j]) for j < S_b and 0 for
+ * S_b <= j <= n_in / step when given.  A non-finite sample leaves that utterance's outputs
+ * unspecified; even then nothing is read or written out of bounds and other utterances are
+ * unaffected.  Results are bit-identical run to run (no floating-point atomics), and no work group
+ * waits on another inside a kernel.
+ *   `workspace` (16-B aligned) of tt2_loudness_workspace_size(batch, n_in, step) bytes holds the
+ * gains, and per segment a state, a peak and its pieces, and the sub-block sums.
+ *   Refused with TT2_E_INVALID before any launch: step < 1 or 4 * step beyond int32; batch, n_in or
+ * n_out negative; x_ld < n_in; y given with y_ld < n_out; energy given with energy_ld < n_in / step
+ * + 1; a coefficient that is not finite; abs_sum negative or not finite; rel_ratio outside [0, 1];
+ * target_ms or ceiling not finite or <= 0; a null x with samples to read (batch and n_in positive);
+ * every output null; a workspace below the size query; more than 2^31 - 1 work groups.  batch = 0
+ * succeeds without a launch. */
+typedef struct tt2_loudness_args {
+  const float* x;          /* [batch, x_ld] */
+  const int32_t* lens;     /* [batch] valid input samples, device, or NULL (= n_in) */
+  float* y;                /* optional [batch, y_ld] */
+  float* loud;             /* optional [batch] */
+  float* gain;             /* optional [batch] */
+  float* peak;             /* optional [batch] */
+  int32_t* limited;        /* optional [batch] */
+  float* energy;           /* optional [batch, energy_ld] */
+  void* workspace; size_t workspace_bytes;
+  int64_t x_ld, y_ld, energy_ld;
+  int32_t batch, n_in, n_out, step;
+  double coef[10];
+  double abs_sum, rel_ratio, target_ms;
+  float ceiling;
+} tt2_loudness_args;
+size_t tt2_loudness_workspace_size(int batch, int n_in, int step);
+int tt2_loudness(const tt2_loudness_args* a, hipStream_t stream);
+
 /* ------------------------------------------------------------------ decode
  * One query row per batch element (the AR decode step):
  * out[b*o_ld + 64h ..] = softmax(scale q k^T) v over keys j < n_b of batch b,

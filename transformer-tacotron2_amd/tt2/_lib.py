@@ -326,6 +326,24 @@ SIGNATURES.update({
 })
 
 
+class LoudnessArgs(C.Structure):
+    """tt2_loudness_args: gated integrated loudness and a gain to a target level under a peak ceiling."""
+    _fields_ = [
+        ("x", vp), ("lens", vp), ("y", vp), ("loud", vp), ("gain", vp), ("peak", vp), ("limited", vp), ("energy", vp),
+        ("workspace", vp), ("workspace_bytes", sz),
+        ("x_ld", i64), ("y_ld", i64), ("energy_ld", i64),
+        ("batch", i32), ("n_in", i32), ("n_out", i32), ("step", i32),
+        ("coef", C.c_double * 10), ("abs_sum", C.c_double), ("rel_ratio", C.c_double), ("target_ms", C.c_double),
+        ("ceiling", f32),
+    ]
+
+
+SIGNATURES.update({
+    "tt2_loudness_workspace_size": ([C.c_int, C.c_int, C.c_int], C.c_size_t),
+    "tt2_loudness": ([C.POINTER(LoudnessArgs), vp], C.c_int),
+})
+
+
 class ReduceArgs(C.Structure):
     _fields_ = [("src", vp), ("dst", vp), ("ld", i64), ("rows", i32), ("cols", i32), ("beta", f32)]
 

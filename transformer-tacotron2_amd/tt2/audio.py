@@ -19,6 +19,10 @@
 * ``SilenceTrimmer``: leading and trailing silence off a batch, by frame energy relative to the
   utterance's loudest frame (tt2_trim; librosa.effects.trim's rule), optionally behind a Resampler:
   the step that VCTK-like corpora need before alignments and stop tokens can be learnt.
+* ``LoudnessNormalizer`` / ``kweighting``: integrated loudness per ITU-R BS.1770-4 of every utterance
+  of a batch and one gain each to a target level under a sample-peak ceiling (tt2_loudness: the
+  K-weighting recurrence as a float64 scan), optionally behind a trimmer and a resampler: the step
+  that makes energies and log-mels of corpora recorded at different levels comparable.
 
 Every transform runs on the GPU through libtt2: the window-folded DFT basis, its
 inverse and the mel filterbank are f32 ``tt2_gemm`` operands (constant tables built
@@ -496,6 +500,141 @@ class SilenceTrimmer:
         """(audio_out [B, L] f32, out_lens [B] int32): the resampler protocol."""
         t = self.trim(audio, lens)
         return t.audio, t.lens
+
+
+def kweighting(sr: int):
+    """The two K-weighting biquads of ITU-R BS.1770 at the rate sr, ((b, a), (b, a)) as tuples of three
+    floats each (a[0] = 1): the high shelf, then the high-pass, from the analogue prototypes by the
+    bilinear transform (the formulas of libebur128 and pyloudnorm).  At 48 kHz they are the
+    standard's own table to 1e-15.  float64 on the host, no device work."""
+    if int(sr) != sr or sr < 1:
+        raise ValueError(f"kweighting: the rate must be a positive integer, got {sr}")
+    f0, G, Q = 1681.974450955533, 3.999843853973347, 0.7071752369554196
+    K = math.tan(math.pi * f0 / sr)
+    Vh = 10.0 ** (G / 20.0)
+    Vb = Vh ** 0.4996667741545416
+    a0 = 1.0 + K / Q + K * K
+    shelf = (((Vh + Vb * K / Q + K * K) / a0, 2.0 * (K * K - Vh) / a0, (Vh - Vb * K / Q + K * K) / a0),
+             (1.0, 2.0 * (K * K - 1.0) / a0, (1.0 - K / Q + K * K) / a0))
+    f0, Q = 38.13547087602444, 0.5003270373238773
+    K = math.tan(math.pi * f0 / sr)
+    a0 = 1.0 + K / Q + K * K
+    highpass = ((1.0, -2.0, 1.0), (1.0, 2.0 * (K * K - 1.0) / a0, (1.0 - K / Q + K * K) / a0))
+    return shelf, highpass
+
+
+class Loudness(NamedTuple):
+    """LoudnessNormalizer.measure(): loud [B] f32 LKFS (-inf: unmeasured), peak [B] f32 max |x|, energy
+    [B, L // step + 1] f32 sums of the squared K-weighted signal per 100 ms."""
+    loud: torch.Tensor
+    peak: torch.Tensor
+    energy: torch.Tensor
+
+
+class Normalized(NamedTuple):
+    """LoudnessNormalizer.normalize(): audio [B, L] f32 (zeros past lens), lens [B] int32, loud [B] f32
+    LKFS of the input, gain [B] f32 (a factor), peak [B] f32 of the input, limited [B] int32 (1: the
+    peak ceiling set the gain)."""
+    audio: torch.Tensor
+    lens: torch.Tensor
+    loud: torch.Tensor
+    gain: torch.Tensor
+    peak: torch.Tensor
+    limited: torch.Tensor
+
+
+class LoudnessNormalizer:
+    """Loudness normalisation of a padded batch (tt2_loudness; include/tt2_capi.h has the definition):
+    integrated loudness per ITU-R BS.1770-4 (K-weighting, 400 ms blocks every 100 ms, the -70 LKFS
+    absolute and the -10 LU relative gate), one gain per utterance that brings it to `target` LKFS
+    unless the sample peak would then pass `peak_db` dBFS, in which case the peak sets the gain
+    (limited).  An utterance with no block above the gates (shorter than 400 ms, silence) is
+    unmeasured and passes unchanged.  No limiter, no true-peak measurement.  The defaults (-23 LUFS,
+    -1 dBFS) are EBU R128's: they were chosen without a speech corpus.  With resampler=rs (any object
+    of the resampler protocol whose sr_out is `sr`, a SilenceTrimmer over a Resampler for one) a call
+    runs rs first, so one object takes a corpus from its own rate to trimmed, levelled audio wherever
+    a resampler is accepted (data.collate, data.resample_corpus, data.normalize_corpus)."""
+
+    def __init__(self, target: float = -23.0, peak_db: float = -1.0, sr: int = SR, resampler=None, device="cuda"):
+        target, peak_db = float(target), float(peak_db)
+        if not (math.isfinite(target) and math.isfinite(peak_db)):
+            raise ValueError(f"LoudnessNormalizer: target and peak_db must be finite, got {target}, {peak_db}")
+        if int(sr) != sr or sr < 10 or sr % 10:
+            raise ValueError(f"LoudnessNormalizer: the rate must be a positive multiple of 10 (100 ms steps), got {sr}")
+        if resampler is not None and int(resampler.sr_out) != int(sr):
+            raise ValueError(f"LoudnessNormalizer: the resampler writes {resampler.sr_out} Hz, the normaliser "
+                             f"works at {sr} Hz")
+        self.target, self.peak_db, self.sr = target, peak_db, int(sr)
+        self.step = self.sr // 10
+        (b1, a1), (b2, a2) = kweighting(self.sr)
+        self.coef = (*b1, a1[1], a1[2], *b2, a2[1], a2[2])
+        self.abs_sum = 4.0 * self.step * 10.0 ** ((-70.0 + 0.691) / 10.0)
+        self.rel_ratio = 0.1
+        self.target_ms = 10.0 ** ((target + 0.691) / 10.0)
+        # the amplitude ratio in float64, rounded once to f32 (the C argument is an f32)
+        self.ceiling = float(torch.tensor(10.0 ** (peak_db / 20.0), dtype=torch.float64).float())
+        self.resampler = resampler
+        self.dev = torch.device(device)
+        self._ws = ops.Workspace()
+
+    sr_in = property(lambda self: self.resampler.sr_in if self.resampler is not None else self.sr)
+    sr_out = property(lambda self: self.sr)
+
+    def params(self) -> dict:
+        p = {"target": self.target, "peak_db": self.peak_db, "sr": self.sr, "step": self.step, "coef": list(self.coef),
+             "abs_sum": self.abs_sum, "rel_ratio": self.rel_ratio, "target_ms": self.target_ms, "ceiling": self.ceiling}
+        if self.resampler is not None:
+            p["resampler"] = self.resampler.params()
+        return p
+
+    def _prepare(self, audio, lens):
+        if self.resampler is not None:
+            audio, lens = self.resampler(audio, lens)
+        audio = audio.to(self.dev, torch.float32)
+        if audio.stride(1) != 1 and audio.shape[1] > 1:
+            audio = audio.contiguous()
+        lens32 = lens.to(self.dev, torch.int32).contiguous() if lens is not None else None
+        return audio, lens32
+
+    def _run(self, audio, lens32, **out):
+        ops.loudness(audio, self.step, self.coef, self.abs_sum, self.rel_ratio, self.target_ms, self.ceiling,
+                     lens=lens32, workspace=self._ws, **out)
+
+    def measure(self, audio: torch.Tensor, lens: torch.Tensor | None = None) -> Loudness:
+        """audio [B, L] f32 at sr_in, lens [B] samples (optional) -> Loudness, fresh tensors; no audio
+        is written.  On the current stream, no host synchronisation."""
+        audio, lens32 = self._prepare(audio, lens)
+        B, L = audio.shape
+        f = dict(dtype=torch.float32, device=self.dev)
+        if B == 0 or L == 0:
+            return Loudness(torch.full((B,), -math.inf, **f), torch.zeros(B, **f), torch.zeros(B, L // self.step + 1, **f))
+        loud, peak = torch.empty(B, **f), torch.empty(B, **f)
+        energy = torch.empty(B, L // self.step + 1, **f)
+        self._run(audio, lens32, loud=loud, peak=peak, energy=energy)
+        return Loudness(loud, peak, energy)
+
+    def normalize(self, audio: torch.Tensor, lens: torch.Tensor | None = None) -> Normalized:
+        """audio [B, L] f32 at sr_in, lens [B] samples (optional) -> Normalized, every field a fresh
+        tensor; the scratch is this object's own, grown on demand.  On the current stream, no host
+        synchronisation."""
+        audio, lens32 = self._prepare(audio, lens)
+        B, L = audio.shape
+        f = dict(dtype=torch.float32, device=self.dev)
+        out_lens = (lens32.clamp(0, L) if lens32 is not None
+                    else torch.full((B,), L, dtype=torch.int32, device=self.dev))
+        if B == 0 or L == 0:
+            return Normalized(torch.zeros(B, L, **f), out_lens, torch.full((B,), -math.inf, **f), torch.ones(B, **f),
+                              torch.zeros(B, **f), torch.zeros(B, dtype=torch.int32, device=self.dev))
+        y = torch.empty(B, L, **f)
+        loud, gain, peak = torch.empty(B, **f), torch.empty(B, **f), torch.empty(B, **f)
+        limited = torch.empty(B, dtype=torch.int32, device=self.dev)
+        self._run(audio, lens32, y=y, loud=loud, gain=gain, peak=peak, limited=limited)
+        return Normalized(y, out_lens, loud, gain, peak, limited)
+
+    def __call__(self, audio: torch.Tensor, lens: torch.Tensor | None = None):
+        """(audio_out [B, L] f32, lens [B] int32): the resampler protocol."""
+        n = self.normalize(audio, lens)
+        return n.audio, n.lens
 
 
 def phoneme_average(values: torch.Tensor, durations: torch.Tensor, mask: torch.Tensor | None = None) -> torch.Tensor:

@@ -23,6 +23,10 @@
 * ``trim_corpus`` (``tools/trim_corpus.py``): the corpus with leading and trailing silence removed by
   ``tt2.audio.SilenceTrimmer`` (which can resample in the same pass), with a ``trim.json`` manifest;
   a SilenceTrimmer also fits ``collate(..., resampler=)`` as it is.
+* ``normalize_corpus`` (``tools/normalize_corpus.py``): the corpus brought to one integrated loudness
+  (ITU-R BS.1770) under a sample-peak ceiling by ``tt2.audio.LoudnessNormalizer`` (which can resample
+  and trim in the same pass), with a ``loudness.json`` manifest; it fits ``collate(..., resampler=)``
+  as well.
 """
 from __future__ import annotations
 
@@ -400,5 +404,83 @@ def trim_corpus(ds: LJSpeech, out_root: str, trimmer, batch_size: int = 16):
                 if line.split("|", 1)[0].rstrip("\r\n") not in gone:
                     g.write(line)
     with open(os.path.join(out_root, "trim.json"), "w") as f:
+        json.dump(manifest, f, indent=1, sort_keys=True)
+    return manifest
+
+
+def normalize_corpus(ds: LJSpeech, out_root: str, normalizer, batch_size: int = 16):
+    """The corpus `ds` brought to one loudness, as a corpus of the same layout under out_root:
+    out_root/wavs/<id>.wav (PCM16 mono at the normaliser's sr_out: rint(x * 32768) clipped to
+    [-32768, 32767]), a copy of metadata.csv, and out_root/loudness.json: {"normalizer": its params(),
+    "utterances": {id: {"samples", "loudness_in" (LKFS; null: unmeasured), "gain_db", "peak_in",
+    "limited", "clipped"}}, "unmeasured": [ids], "empty": [ids], "stats": {"measured",
+    "mean_loudness_in", "min_loudness_in", "max_loudness_in", "limited"}}.  An unmeasured utterance (no
+    400 ms block above the gates: too short, or silence) is written at gain 1 and listed under
+    "unmeasured"; the statistics run over the measured ones (null where there is none).  `samples`
+    counts samples at sr_out (after the normaliser's resampler or trimmer, when it has one); an
+    utterance that a trimmer in front left nothing of is listed under "empty" as well, not written,
+    and its line is left out of the copied metadata.csv, as trim_corpus does.  `normalizer` is a
+    tt2.audio.LoudnessNormalizer whose sr_in is ds.sr, or any object with sr_in, sr_out, params() and
+    normalize(audio [B, L], lens [B]) -> (audio, lens, loud, gain, peak, limited): one call per batch
+    of batch_size utterances in corpus order.  Returns the manifest."""
+    import math
+    import shutil
+    from scipy.io import wavfile
+    if int(normalizer.sr_in) != int(getattr(ds, "sr", 22050)):
+        raise ValueError(f"normalize_corpus: the normaliser reads {normalizer.sr_in} Hz, the corpus is at "
+                         f"{getattr(ds, 'sr', 22050)} Hz")
+    if batch_size < 1:
+        raise ValueError("normalize_corpus: batch_size must be at least 1")
+    if os.path.abspath(out_root) == os.path.abspath(ds.root):
+        raise ValueError("normalize_corpus: out_root is the corpus itself")
+    os.makedirs(os.path.join(out_root, "wavs"), exist_ok=True)
+    dev = getattr(normalizer, "dev", "cpu")
+    manifest = {"normalizer": normalizer.params() if hasattr(normalizer, "params") else {}, "utterances": {},
+                "unmeasured": [], "empty": []}
+    measured, n_limited = [], 0
+    for s in range(0, len(ds), batch_size):
+        idx = list(range(s, min(s + batch_size, len(ds))))
+        wavs = [ds.wav(i) for i in idx]
+        audio = torch.zeros(len(idx), max(len(w) for w in wavs), dtype=torch.float32)
+        for b, w in enumerate(wavs):
+            audio[b, :len(w)] = torch.from_numpy(w)
+        lens = torch.tensor([len(w) for w in wavs], dtype=torch.int32)
+        y, out_lens, loud, gain, peak, limited = normalizer.normalize(audio.to(dev), lens.to(dev))[:6]
+        y = torch.as_tensor(y).detach().float().cpu().numpy()
+        out_lens = [int(n) for n in torch.as_tensor(out_lens).cpu()]
+        loud, gain, peak = ([float(v) for v in torch.as_tensor(t).cpu()] for t in (loud, gain, peak))
+        limited = [int(v) for v in torch.as_tensor(limited).cpu()]
+        for b, i in enumerate(idx):
+            uid = str(ds.items[i][0])
+            q = np.rint(y[b, :out_lens[b]].astype(np.float64) * 32768.0)
+            clipped = int(((q < -32768) | (q > 32767)).sum())
+            ok = math.isfinite(loud[b])
+            manifest["utterances"][uid] = {"samples": out_lens[b], "loudness_in": loud[b] if ok else None,
+                                           "gain_db": 20.0 * math.log10(gain[b]) if gain[b] > 0 else None,
+                                           "peak_in": peak[b], "limited": bool(limited[b]), "clipped": clipped}
+            if ok:
+                measured.append(loud[b])
+                n_limited += limited[b]
+            else:
+                manifest["unmeasured"].append(uid)
+            if out_lens[b] == 0:
+                manifest["empty"].append(uid)
+                continue
+            wavfile.write(os.path.join(out_root, "wavs", uid + ".wav"), int(normalizer.sr_out),
+                          np.clip(q, -32768, 32767).astype(np.int16))
+    manifest["stats"] = {"measured": len(measured), "limited": n_limited,
+                         "mean_loudness_in": sum(measured) / len(measured) if measured else None,
+                         "min_loudness_in": min(measured) if measured else None,
+                         "max_loudness_in": max(measured) if measured else None}
+    src, dst = os.path.join(ds.root, "metadata.csv"), os.path.join(out_root, "metadata.csv")
+    if not manifest["empty"]:
+        shutil.copyfile(src, dst)
+    else:
+        gone = set(manifest["empty"])
+        with open(src, encoding="utf-8", newline="") as f, open(dst, "w", encoding="utf-8", newline="") as g:
+            for line in f:
+                if line.split("|", 1)[0].rstrip("\r\n") not in gone:
+                    g.write(line)
+    with open(os.path.join(out_root, "loudness.json"), "w") as f:
         json.dump(manifest, f, indent=1, sort_keys=True)
     return manifest

@@ -812,6 +812,76 @@ def trim(x, y, hop, r, keep, ratio, lens=None, out_lens=None, start=None, energy
     return y, out_lens, start, energy
 
 
+def loudness(x, step, coef, abs_sum, rel_ratio, target_ms, ceiling, lens=None, y=None, loud=None, gain=None,
+             peak=None, limited=None, energy=None, workspace=None):
+    """Gated integrated loudness and gain (tt2_loudness_args; include/tt2_capi.h has the definition):
+    x [B, n_in] f32 through the two biquads of coef (ten floats: b0 b1 b2 a1 a2 of each section),
+    sub-block energies of `step` samples, blocks of four, the absolute gate abs_sum (a block's sum of
+    squares) and the relative gate rel_ratio, the gain min(sqrt(target_ms / ms), ceiling / peak).
+    Every output is optional, at least one is required: y [B, n_out] f32 = gain * x (zeros past the
+    utterance), loud / gain / peak [B] f32, limited [B] int32, energy [B, >= n_in // step + 1] f32.  x, y
+    and energy are 2-D with a contiguous last dim (row views are fine).  lens [B] int32 bounds the
+    valid samples (None: n_in).  workspace: a Workspace (default: the module's).  On the current
+    stream, no host synchronisation.  Deterministic."""
+    import math
+    who = "loudness"
+    step = int(step)
+    coef = [float(c) for c in coef]
+    abs_sum, rel_ratio, target_ms, ceiling = float(abs_sum), float(rel_ratio), float(target_ms), float(ceiling)
+    if step < 1 or 4 * step > 2 ** 31 - 1:
+        raise _lib.TT2Error(f"{who}: step >= 1 and 4 * step within int32, got {step}")
+    if len(coef) != 10 or not all(math.isfinite(c) for c in coef):
+        raise _lib.TT2Error(f"{who}: coef must be ten finite numbers")
+    if not (math.isfinite(abs_sum) and abs_sum >= 0.0) or not (0.0 <= rel_ratio <= 1.0):
+        raise _lib.TT2Error(f"{who}: abs_sum finite and >= 0 and 0 <= rel_ratio <= 1, got {abs_sum}, {rel_ratio}")
+    if not (math.isfinite(target_ms) and target_ms > 0.0 and math.isfinite(ceiling) and ceiling > 0.0):
+        raise _lib.TT2Error(f"{who}: target_ms and ceiling finite and > 0, got {target_ms}, {ceiling}")
+    vecs = [(n, t) for n, t in (("loud", loud), ("gain", gain), ("peak", peak), ("limited", limited)) if t is not None]
+    views = [(n, t) for n, t in (("x", x), ("y", y), ("energy", energy)) if t is not None]
+    if len(views) == 1 and not vecs:
+        raise _lib.TT2Error(f"{who}: at least one output is required")
+    for name, t in views:
+        if t.dtype != torch.float32 or t.dim() != 2 or (t.shape[1] > 1 and t.stride(1) != 1):
+            raise _lib.TT2Error(f"{who}: {name} must be f32 [rows, cols] with a contiguous last dim")
+        if t.shape[0] != x.shape[0]:
+            raise _lib.TT2Error(f"{who}: {name} has {t.shape[0]} rows, x {x.shape[0]}")
+    B, n_in = x.shape
+    n_out = y.shape[1] if y is not None else 0
+    if energy is not None and energy.shape[1] < n_in // step + 1:
+        raise _lib.TT2Error(f"{who}: energy needs {n_in // step + 1} columns, got {energy.shape[1]}")
+
+    def ld(t):   # a single row's stride is arbitrary: any value that covers the row
+        return t.stride(0) if t.shape[0] > 1 else max(t.stride(0), t.shape[1])
+
+    for name, t in views:
+        if ld(t) < t.shape[1]:
+            raise _lib.TT2Error(f"{who}: {name}'s rows overlap (stride {t.stride(0)} below {t.shape[1]} columns)")
+    tensors = [t for _, t in views]
+    for name, t in vecs + ([("lens", lens)] if lens is not None else []):
+        _need(f"{who}: {name}", t, B, torch.int32 if name in ("lens", "limited") else torch.float32)
+        if not t.is_contiguous():
+            raise _lib.TT2Error(f"{who}: {name} must be contiguous")
+        tensors.append(t)
+    for t in tensors:
+        if t.device != x.device or not t.is_cuda:
+            raise _lib.TT2Error(f"{who}: every tensor must be on x's GPU")
+    g = _lib.LoudnessArgs()
+    g.x, g.lens, g.y = x.data_ptr(), ptr(lens), ptr(y)
+    g.loud, g.gain, g.peak, g.limited, g.energy = ptr(loud), ptr(gain), ptr(peak), ptr(limited), ptr(energy)
+    g.x_ld, g.y_ld = ld(x), (ld(y) if y is not None else 0)
+    g.energy_ld = ld(energy) if energy is not None else 0
+    g.batch, g.n_in, g.n_out, g.step = B, n_in, n_out, step
+    g.coef = (C.c_double * 10)(*coef)
+    g.abs_sum, g.rel_ratio, g.target_ms, g.ceiling = abs_sum, rel_ratio, target_ms, ceiling
+    L = lib()
+    need = L.tt2_loudness_workspace_size(B, n_in, step)
+    if need:
+        buf = (workspace or _WS).get(need)
+        g.workspace, g.workspace_bytes = buf.data_ptr(), buf.numel()
+    check(L.tt2_loudness(C.byref(g), stream_ptr()), "tt2_loudness")
+    return y, loud, gain, peak, limited, energy
+
+
 def _drop_into(s, drop: Drop):
     s.drop_seed, s.drop_site, s.drop_thr, s.drop_scale = drop.fields()
 
