@@ -672,6 +672,74 @@ typedef struct tt2_loudness_args {
 size_t tt2_loudness_workspace_size(int batch, int n_in, int step);
 int tt2_loudness(const tt2_loudness_args* a, hipStream_t stream);
 
+/* ---------------------------------------------------------- length regulator
+ * Phoneme states and integer durations to frame states (FastSpeech's length regulator), and the
+ * gradient of that expansion: three entries, one launch each, no workspace, no host synchronisation,
+ * no floating-point atomics; results are bit-identical run to run.
+ *   tt2_regulate_plan.  For utterance b, Tx_b = clamp(key_len[b], 0, tx) (key_len NULL: tx) and
+ * d'[b][t] = max(durations[b][t], 0) for t < Tx_b; entries at t >= Tx_b are not read and count as 0.
+ * S[b][t] is the sum of d'[b][u] over u <= t in 64-bit integers (two phonemes of 2^31 - 1 frames do
+ * not wrap).  ends[b][t] = min(S[b][t], n_out) is written for every t < tx, so it is constant from
+ * Tx_b - 1 on and all 0 when Tx_b = 0.  frames[b] = ends[b][tx - 1] (0 when tx = 0);
+ * total[b] = min(S[b][tx - 1], 2^31 - 1) (0 when tx = 0), so that total > frames shows a truncation
+ * at n_out.  index[b][n] is the lowest t with ends[b][t] > n for n < frames[b] (a phoneme of zero
+ * duration owns no frame) and -1 for frames[b] <= n < n_out.  index, frames and total are optional;
+ * nothing is written at or past column tx of ends or column n_out of index.  One work group scans
+ * one utterance with its ends in LDS, which is the limit tx <= TT2_REGULATE_MAX_PHONEMES (16 KB).
+ *   tt2_regulate_fwd (map = index).  y[b][n][c] = h[b][index[b][n]][c] where 0 <= index[b][n] < tx,
+ * the element's bits copied (-0, denormals, infinities and NaN payloads survive), and exactly +0
+ * where the index is outside [0, tx), for n < n_out and c < dim; src = h, dst = y.  Nothing is
+ * written at or past column dim of a row or row n_out of an utterance; whatever index holds, nothing
+ * is read out of bounds; rows of h that no frame names are not read.
+ *   tt2_regulate_bwd (map = ends).  With s = clamp(ends[b][t-1], 0, n_out) (0 for t = 0) and
+ * e = clamp(ends[b][t], 0, n_out): dh[b][t][c] = from_f32(acc), where the f32 accumulator acc starts
+ * at +0 and adds to_f32(dy[b][n][c]) for n = s, s + 1, .., e - 1 in ascending n, one IEEE f32 add
+ * each (no contraction, no reordering), and is rounded once, to nearest even, to the output dtype at
+ * the end; e <= s gives exactly +0.  src = dy, dst = dh.  dh is written for every t < tx and c < dim
+ * (the rows past Tx_b hold +0: ends is constant there); rows of dy at or past ends[b][tx - 1] are not
+ * read (ends as tt2_regulate_plan writes them).  Every bit of dh is thereby defined for any input.
+ * This is the gradient of the expansion with respect to h, and on its own the sum of frame values
+ * per phoneme.  The cost of a phoneme is proportional to its duration and a phoneme is summed by one
+ * lane per column, so the longest phoneme of a launch is its tail; long runs are not split, because
+ * that would change the order of the sum.
+ *   Row element (b, r, c) of src or dst is at base + b * bs + r * ld + c, in elements of `dtype`
+ * (TT2_DT_F32 or TT2_DT_BF16, the same for both): activations may be column slices of wider
+ * buffers.  Any dim and any element alignment work; rows move in 16-byte chunks where both bases sit
+ * on 16 bytes and every ld, bs and dim is a whole number of chunks, element by element otherwise,
+ * with the same result.
+ *   Refused with TT2_E_INVALID before any launch, with a message that starts with the entry's name:
+ * null args; batch, tx, n_out or dim negative; tx > TT2_REGULATE_MAX_PHONEMES; dur_ld < tx,
+ * ends_ld < tx, index given with index_ld < n_out (plan); src_ld < dim, dst_ld < dim, map_ld < n_out
+ * (fwd) or < tx (bwd); a dtype other than f32 / bf16; more than 2^31 - 1 work groups; then, where
+ * the call has something to do, a null pointer it would read or write: durations or ends with
+ * tx > 0 (plan), dst, and src or map with tx > 0 (fwd) or n_out > 0 (bwd).
+ *   Zero sizes.  batch = 0 succeeds without a launch, in all three.  plan with n_out = 0 still writes
+ * ends (all 0), frames and total; with tx = 0 it writes frames = total = 0 and index = -1.  fwd with
+ * n_out = 0 or dim = 0 succeeds without a launch, and with tx = 0 writes +0 to every row (src and
+ * map may be NULL).  bwd with tx = 0 or dim = 0 succeeds without a launch, and with n_out = 0 writes
+ * +0 to every row of dh (src and map may be NULL). */
+#define TT2_REGULATE_MAX_PHONEMES 4096
+typedef struct tt2_regulate_plan_args {
+  const int32_t* durations;  /* [batch, dur_ld] */
+  const int32_t* key_len;    /* [batch] valid phonemes, device, or NULL (= tx) */
+  int32_t* ends;             /* [batch, ends_ld] */
+  int32_t* index;            /* optional [batch, index_ld] */
+  int32_t* frames;           /* optional [batch] */
+  int32_t* total;            /* optional [batch] */
+  int64_t dur_ld, ends_ld, index_ld;
+  int32_t batch, tx, n_out;
+} tt2_regulate_plan_args;
+typedef struct tt2_regulate_args {
+  const void* src;           /* fwd: h [batch, tx, dim]; bwd: dy [batch, n_out, dim] */
+  void* dst;                 /* fwd: y [batch, n_out, dim]; bwd: dh [batch, tx, dim] */
+  const int32_t* map;        /* fwd: index [batch, map_ld]; bwd: ends [batch, map_ld] */
+  int64_t src_ld, src_bs, dst_ld, dst_bs, map_ld;   /* row and batch strides, in elements */
+  int32_t batch, tx, n_out, dim, dtype;
+} tt2_regulate_args;
+int tt2_regulate_plan(const tt2_regulate_plan_args* a, hipStream_t stream);
+int tt2_regulate_fwd(const tt2_regulate_args* a, hipStream_t stream);
+int tt2_regulate_bwd(const tt2_regulate_args* a, hipStream_t stream);
+
 /* ------------------------------------------------------------------ decode
  * One query row per batch element (the AR decode step):
  * out[b*o_ld + 64h ..] = softmax(scale q k^T) v over keys j < n_b of batch b,

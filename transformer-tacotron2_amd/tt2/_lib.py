@@ -344,6 +344,34 @@ SIGNATURES.update({
 })
 
 
+REGULATE_MAX_PHONEMES = 4096   # TT2_REGULATE_MAX_PHONEMES: one work group's ends in LDS
+
+
+class RegulatePlanArgs(C.Structure):
+    """tt2_regulate_plan_args: durations -> segment ends, frame -> phoneme index, frame counts."""
+    _fields_ = [
+        ("durations", vp), ("key_len", vp), ("ends", vp), ("index", vp), ("frames", vp), ("total", vp),
+        ("dur_ld", i64), ("ends_ld", i64), ("index_ld", i64),
+        ("batch", i32), ("tx", i32), ("n_out", i32),
+    ]
+
+
+class RegulateArgs(C.Structure):
+    """tt2_regulate_args: the expansion (map = index) or the segment sum (map = ends)."""
+    _fields_ = [
+        ("src", vp), ("dst", vp), ("map", vp),
+        ("src_ld", i64), ("src_bs", i64), ("dst_ld", i64), ("dst_bs", i64), ("map_ld", i64),
+        ("batch", i32), ("tx", i32), ("n_out", i32), ("dim", i32), ("dtype", i32),
+    ]
+
+
+SIGNATURES.update({
+    "tt2_regulate_plan": ([C.POINTER(RegulatePlanArgs), vp], C.c_int),
+    "tt2_regulate_fwd": ([C.POINTER(RegulateArgs), vp], C.c_int),
+    "tt2_regulate_bwd": ([C.POINTER(RegulateArgs), vp], C.c_int),
+})
+
+
 class ReduceArgs(C.Structure):
     _fields_ = [("src", vp), ("dst", vp), ("ld", i64), ("rows", i32), ("cols", i32), ("beta", f32)]
 

@@ -882,6 +882,122 @@ def loudness(x, step, coef, abs_sum, rel_ratio, target_ms, ceiling, lens=None, y
     return y, loud, gain, peak, limited, energy
 
 
+def _rg_rows(who, name, t, rows, cols, dtype=torch.int32):
+    """A [rows, >= cols] view of `dtype` with a contiguous last dim; returns its leading dimension."""
+    if t.dtype != dtype or t.dim() != 2 or t.shape[0] != rows or t.shape[1] < cols:
+        raise ValueError(f"{who}: {name} must be {dtype} [{rows}, >= {cols}], got {t.dtype} {tuple(t.shape)}")
+    if t.shape[1] > 1 and t.stride(1) != 1:
+        raise ValueError(f"{who}: {name} needs a contiguous last dim")
+    ld = t.stride(0) if rows > 1 else max(t.stride(0), t.shape[1])   # a single row's stride is arbitrary
+    if ld < t.shape[1]:
+        raise ValueError(f"{who}: {name}'s rows overlap (stride {t.stride(0)} below {t.shape[1]} columns)")
+    return ld
+
+
+def _rg_vec(who, name, t, rows):
+    if t is not None and (t.dtype != torch.int32 or t.dim() != 1 or t.shape[0] != rows or not t.is_contiguous()):
+        raise ValueError(f"{who}: {name} must be a contiguous int32 [{rows}], got {t.dtype} {tuple(t.shape)}")
+
+
+def _rg_same_gpu(who, tensors):
+    dev = tensors[0].device
+    for t in tensors:
+        if t is not None and (not t.is_cuda or t.device != dev):
+            raise ValueError(f"{who}: every tensor must be on the same GPU")
+
+
+def regulate_plan(durations, n_out, key_len=None, ends=None, index=None, frames=None, total=None):
+    """The plan of a length regulator (tt2_regulate_plan_args; include/tt2_capi.h has the definition):
+    durations [B, Tx] int32 (negatives count as 0; entries at and past key_len[b] are not read) ->
+    ends [B, Tx] int32 = min(cumsum, n_out), index [B, n_out] int32 (the phoneme of each frame, -1 past
+    the utterance's frames), frames [B] = ends[:, -1] and total [B] = the unclamped sum (up to 2^31 - 1).
+    ends is required and written for every column; index, frames and total are written where given.
+    2-D tensors need a contiguous last dim (row views are fine).  On the current stream, no host
+    synchronisation.  Deterministic."""
+    who = "regulate_plan"
+    n_out = int(n_out)
+    if durations.dim() != 2 or durations.dtype != torch.int32:
+        raise ValueError(f"{who}: durations must be int32 [B, Tx], got {durations.dtype} {tuple(durations.shape)}")
+    B, tx = durations.shape
+    if tx > _lib.REGULATE_MAX_PHONEMES:
+        raise ValueError(f"{who}: Tx = {tx} above TT2_REGULATE_MAX_PHONEMES = {_lib.REGULATE_MAX_PHONEMES}")
+    if not (0 <= n_out <= 2 ** 31 - 1):
+        raise ValueError(f"{who}: n_out must be in [0, 2^31 - 1], got {n_out}")
+    if ends is None:
+        raise ValueError(f"{who}: ends is required")
+    g = _lib.RegulatePlanArgs()
+    g.dur_ld = _rg_rows(who, "durations", durations, B, tx)
+    g.ends_ld = _rg_rows(who, "ends", ends, B, tx)
+    if index is not None:
+        g.index_ld = _rg_rows(who, "index", index, B, n_out)
+    for name, t in (("key_len", key_len), ("frames", frames), ("total", total)):
+        _rg_vec(who, name, t, B)
+    _rg_same_gpu(who, [durations, ends, index, key_len, frames, total])
+    g.durations, g.key_len, g.ends, g.index = durations.data_ptr(), ptr(key_len), ends.data_ptr(), ptr(index)
+    g.frames, g.total = ptr(frames), ptr(total)
+    g.batch, g.tx, g.n_out = B, tx, n_out
+    check(lib().tt2_regulate_plan(C.byref(g), stream_ptr()), "tt2_regulate_plan")
+    return ends, index, frames, total
+
+
+def _regulate_args(who, src, dst, map_, map_cols):
+    for name, t in (("src", src), ("dst", dst)):
+        if t.dim() != 3 or t.dtype not in (torch.float32, torch.bfloat16):
+            raise ValueError(f"{who}: {name} must be f32 or bf16 [B, rows, D], got {t.dtype} {tuple(t.shape)}")
+    if src.dtype != dst.dtype:
+        raise ValueError(f"{who}: src is {src.dtype}, dst {dst.dtype}")
+    B, D = dst.shape[0], dst.shape[2]
+    if src.shape[0] != B or src.shape[2] != D:
+        raise ValueError(f"{who}: src is {tuple(src.shape)}, dst {tuple(dst.shape)}")
+    g = _lib.RegulateArgs()
+    strides = []
+    for name, t in (("src", src), ("dst", dst)):
+        if D > 1 and t.stride(2) != 1:
+            raise ValueError(f"{who}: {name} needs a contiguous last dim")
+        ld = t.stride(1) if t.shape[1] > 1 else max(t.stride(1), D)
+        bs = t.stride(0) if B > 1 else max(t.stride(0), 0)
+        if ld < D or (name == "dst" and B > 1 and t.shape[1] > 0 and bs < (t.shape[1] - 1) * ld + D):
+            raise ValueError(f"{who}: {name}'s rows overlap (strides {t.stride()} for {tuple(t.shape)})")
+        strides += [ld, bs]
+    g.src_ld, g.src_bs, g.dst_ld, g.dst_bs = strides
+    g.map_ld = _rg_rows(who, "map", map_, B, map_cols)
+    _rg_same_gpu(who, [dst, src, map_])
+    g.src, g.dst, g.map = src.data_ptr(), dst.data_ptr(), map_.data_ptr()
+    g.batch, g.dim, g.dtype = B, D, dt(dst)
+    return g
+
+
+def regulate_fwd(h, index, y):
+    """The expansion of a length regulator (tt2_regulate_fwd): y[b, n, :] = h[b, index[b, n], :], the
+    bits copied, and +0 where index[b, n] is outside [0, Tx).  h [B, Tx, D] and y [B, n_out, D], both
+    f32 or both bf16, may be slices of wider buffers (any row and batch stride, a contiguous last
+    dim); index [B, >= n_out] int32 as regulate_plan writes it.  On the current stream, no host
+    synchronisation.  Deterministic."""
+    who = "regulate_fwd"
+    if h.dim() == 3 and h.shape[1] > _lib.REGULATE_MAX_PHONEMES:
+        raise ValueError(f"{who}: Tx = {h.shape[1]} above TT2_REGULATE_MAX_PHONEMES = {_lib.REGULATE_MAX_PHONEMES}")
+    g = _regulate_args(who, h, y, index, y.shape[1] if y.dim() == 3 else 0)
+    g.tx, g.n_out = h.shape[1], y.shape[1]
+    check(lib().tt2_regulate_fwd(C.byref(g), stream_ptr()), "tt2_regulate_fwd")
+    return y
+
+
+def regulate_bwd(dy, ends, dh):
+    """The segment sum of a length regulator (tt2_regulate_bwd), the gradient of regulate_fwd in h:
+    dh[b, t, :] = the sum of dy[b, n, :] over ends[b, t-1] <= n < ends[b, t] (ends clamped to
+    [0, n_out], 0 before t = 0), added in f32 in ascending n and rounded once to dh's dtype; +0 for an
+    empty segment.  dy [B, n_out, D] and dh [B, Tx, D], both f32 or both bf16, may be slices of wider
+    buffers; ends [B, >= Tx] int32 as regulate_plan writes it.  A phoneme's sum is serial in its
+    duration.  On the current stream, no host synchronisation.  Deterministic."""
+    who = "regulate_bwd"
+    if dh.dim() == 3 and dh.shape[1] > _lib.REGULATE_MAX_PHONEMES:
+        raise ValueError(f"{who}: Tx = {dh.shape[1]} above TT2_REGULATE_MAX_PHONEMES = {_lib.REGULATE_MAX_PHONEMES}")
+    g = _regulate_args(who, dy, dh, ends, dh.shape[1] if dh.dim() == 3 else 0)
+    g.tx, g.n_out = dh.shape[1], dy.shape[1]
+    check(lib().tt2_regulate_bwd(C.byref(g), stream_ptr()), "tt2_regulate_bwd")
+    return dh
+
+
 def _drop_into(s, drop: Drop):
     s.drop_seed, s.drop_site, s.drop_thr, s.drop_scale = drop.fields()
 
