@@ -28,14 +28,11 @@ import statistics
 import sys
 import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "tools"))
-sys.path.insert(0, os.path.join(ROOT, "tests"))
-sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
-from gemm_ab import graph_of, time_graph  # noqa: E402
+from _bench import timed_rounds, wall_us  # noqa: E402
 
 B, NCOEF = 16, 13
 CLOCK_GHZ = 2.4
@@ -53,19 +50,6 @@ def torch_dp(ch, cr):
         best = torch.minimum(torch.minimum(D[:, i, j], D[:, i, j + 1]), D[:, i + 1, j])
         D[:, i + 1, j + 1] = c[:, i, j] + best
     return D[:, n, m]
-
-
-def evicted_us(fn, trash, reps):
-    out = []
-    for _ in range(reps):
-        trash.add_(1.0)
-        e = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
-        e[0].record()
-        fn()
-        e[1].record()
-        torch.cuda.synchronize()
-        out.append(e[0].elapsed_time(e[1]) * 1e3)
-    return min(out)
 
 
 def main():
@@ -113,19 +97,9 @@ def main():
                  "mean_path_cells": float(length.float().mean())}
 
         fns = {"dtw": dtw, "dtw_path": dtw_path, "dct": dct, "mcd_dtw": mcd}
-        graphs = {k: graph_of(f) for k, f in fns.items()}
-        res_us = {k: [] for k in fns}
-        evi_us = {k: [] for k in fns}
         tdp = []
-        for _ in range(a.rounds):   # interleaved: drift of the machine hits every path alike
-            for k in fns:
-                res_us[k].append(time_graph(graphs[k]) * 1e6)
-                evi_us[k].append(evicted_us(fns[k], trash, 3))
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            torch_dp(ch, cr)
-            torch.cuda.synchronize()
-            tdp.append((time.perf_counter() - t0) * 1e6)
+        res_us, evi_us = timed_rounds(fns, a.rounds, trash,
+                                      each_round=lambda: tdp.append(wall_us(lambda: torch_dp(ch, cr))))
         best = {k: min(v) for k, v in res_us.items()}
         stages = (th + 31) // 32 + (tr + 63) // 64 - 1   # tb <= 1024: 32-row x 64-column tiles
         ticks = stages * (32 + 63)

@@ -34,18 +34,13 @@ import statistics
 import sys
 import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "tools"))
-sys.path.insert(0, os.path.join(ROOT, "tests"))
-sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
-from gemm_ab import graph_of, time_graph  # noqa: E402
-from pitch_bench import evicted_us, speech_like  # noqa: E402
+from _bench import HBM_GBPS, speech_like, timed_rounds  # noqa: E402
 
 B, N, SR = 16, 204544, 22050
-HBM_GBPS = 6290.0     # measured float4 copy rate of one MI355X (the guide's figure)
 
 
 def levelled_speech():
@@ -62,19 +57,6 @@ def impulse_response(coef, floor=1e-12):
     last = int(np.nonzero(np.abs(h) >= floor)[0].max())
     assert last < len(h) - 1
     return h[:last + 1]
-
-
-def eager_us(fn, n=10):
-    """us per run of n back-to-back eager runs (launch overhead included)."""
-    fn()
-    torch.cuda.synchronize()
-    e = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
-    e[0].record()
-    for _ in range(n):
-        fn()
-    e[1].record()
-    torch.cuda.synchronize()
-    return e[0].elapsed_time(e[1]) * 1e3 / n
 
 
 class TorchLoudness:
@@ -166,14 +148,8 @@ def main():
              "loud": [round(float(loud.min()), 3), round(float(loud.max()), 3)], "limited": int(lim.sum()),
              "blocks_passing": [int(o.sum()) for o in own][:4], "torch_taps": tl.taps, "torch_nfft": tl.nfft}
     fns = {"loudness": loudness, "normalizer": normalizer, "torch": torch_base}
-    graphs = {k: graph_of(f) for k, f in fns.items() if k != "torch"}     # (the FFTs are not captured: timed eagerly)
-    res_us = {k: [] for k in fns}
-    evi_us = {k: [] for k in fns}
-    trash = torch.zeros(1 << 28, device=dev)
-    for _ in range(a.rounds):   # interleaved: drift of the machine hits every path alike
-        for k in fns:
-            res_us[k].append(time_graph(graphs[k]) * 1e6 if k in graphs else eager_us(fns[k]))
-            evi_us[k].append(evicted_us(fns[k], trash, 3))
+    # (the FFTs are not captured: timed eagerly)
+    res_us, evi_us = timed_rounds(fns, a.rounds, torch.zeros(1 << 28, device=dev), eager=("torch",), eager_runs=10)
     best = {k: min(v) for k, v in res_us.items()}
     evi = {k: min(v) for k, v in evi_us.items()}
     nbytes = 4 * (2 * int(lens.sum()) + B * N)

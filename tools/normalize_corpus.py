@@ -19,44 +19,29 @@ The defaults (-23 LUFS, -1 dBFS) are EBU R128's; they were chosen without a spee
     python tools/normalize_corpus.py --in /data/VCTK-lj --out /data/VCTK-22k-norm --sr-in 48000 \
         [--target -23] [--peak-db -1] [--trim [--top-db 60] [--frame 2048] [--hop 512] [--keep 0]] [--batch 16]
 """
-import argparse
 import json
 import os
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "transformer-tacotron2_amd"))
-
-SR = 22050
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import _corpus_cli as cli  # noqa: E402
 
 
 def parse_args(argv=None):
-    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("--in", dest="src", required=True, help="corpus root (metadata.csv, wavs/) at --sr-in")
-    ap.add_argument("--out", required=True, help="root of the normalised corpus")
-    ap.add_argument("--sr-in", type=int, default=SR, help="sample rate of the corpus' files (other than 22050: resampled first)")
-    ap.add_argument("--target", type=float, default=-23.0, help="integrated loudness to reach, LKFS")
-    ap.add_argument("--peak-db", type=float, default=-1.0, help="sample-peak ceiling after the gain, dBFS")
-    ap.add_argument("--trim", action="store_true", help="remove leading and trailing silence first")
-    ap.add_argument("--top-db", type=float, default=60.0, help="--trim: frames this far below the loudest one are silence")
-    ap.add_argument("--frame", type=int, default=2048, help="--trim: frame length in samples at 22.05 kHz")
-    ap.add_argument("--hop", type=int, default=512, help="--trim: frame hop in samples at 22.05 kHz")
-    ap.add_argument("--keep", type=int, default=0, help="--trim: samples kept either side of the loud stretch")
-    ap.add_argument("--batch", type=int, default=16)
-    return ap.parse_args(argv)
+    def own(ap):
+        ap.add_argument("--target", type=float, default=-23.0, help="integrated loudness to reach, LKFS")
+        ap.add_argument("--peak-db", type=float, default=-1.0, help="sample-peak ceiling after the gain, dBFS")
+        ap.add_argument("--trim", action="store_true", help="remove leading and trailing silence first")
+    return cli.parse_args(__doc__, "normalised", argv, own, trim="--trim: ")
 
 
 def main(argv=None):
     a = parse_args(argv)
-    from tt2.audio import LoudnessNormalizer, Resampler, SilenceTrimmer
+    from tt2.audio import LoudnessNormalizer
     from tt2.data import LJSpeech, normalize_corpus
 
-    ds = LJSpeech(a.src, sr=a.sr_in)
-    front = Resampler(a.sr_in, SR) if a.sr_in != SR else None
-    if a.trim:
-        front = SilenceTrimmer(top_db=a.top_db, frame=a.frame, hop=a.hop, keep=a.keep, sr=SR, resampler=front)
-    nz = LoudnessNormalizer(target=a.target, peak_db=a.peak_db, sr=SR, resampler=front)
-    man = normalize_corpus(ds, a.out, nz, batch_size=a.batch)
+    nz = LoudnessNormalizer(target=a.target, peak_db=a.peak_db, sr=cli.SR, resampler=cli.build_front(a, trim=a.trim))
+    man = normalize_corpus(LJSpeech(a.src, sr=a.sr_in), a.out, nz, batch_size=a.batch)
     utts = man["utterances"].values()
     print(json.dumps({"out": a.out, "utterances": len(utts), "target": a.target, "peak_db": a.peak_db,
                       "stats": man["stats"], "unmeasured": len(man["unmeasured"]),

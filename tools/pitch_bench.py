@@ -24,37 +24,19 @@ Prints one JSON line (and writes it to --out).
 """
 import argparse
 import json
-import math
 import os
 import statistics
 import sys
 import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "tools"))
-sys.path.insert(0, os.path.join(ROOT, "tests"))
-sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
-from gemm_ab import graph_of, time_graph  # noqa: E402
+from _bench import speech_like, timed_rounds, wall_us  # noqa: E402
 
 B, T = 16, 800
 CLOCK_GHZ, SIMDS = 2.4, 1024
-
-
-def speech_like(B, L, seed=0):
-    """Voiced stretches with a gliding pitch and three harmonics, noisy stretches between them."""
-    g = torch.Generator().manual_seed(seed)
-    t = torch.arange(L, dtype=torch.float64) / 22050.0
-    out = torch.zeros(B, L, dtype=torch.float64)
-    for b in range(B):
-        f = 90.0 + 20.0 * b + 30.0 * torch.sin(2 * math.pi * (0.7 + 0.05 * b) * t)
-        ph = 2 * math.pi * torch.cumsum(f, 0) / 22050.0
-        tone = 0.3 * torch.sin(ph) + 0.15 * torch.sin(2 * ph + 0.5) + 0.08 * torch.sin(3 * ph + 1.1)
-        voiced = (torch.sin(2 * math.pi * 1.3 * t + b) > -0.3).double()
-        out[b] = tone * voiced + (0.01 + 0.1 * (1 - voiced)) * torch.randn(L, generator=g, dtype=torch.float64)
-    return out.float()
 
 
 def torch_cmnd(padded, Lp, tau_max):
@@ -72,19 +54,6 @@ def torch_cmnd(padded, Lp, tau_max):
         cm[:, 0] = 1
         out.append(cm)
     return torch.stack(out)
-
-
-def evicted_us(fn, trash, reps):
-    out = []
-    for _ in range(reps):
-        trash.add_(1.0)
-        e = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
-        e[0].record()
-        fn()
-        e[1].record()
-        torch.cuda.synchronize()
-        out.append(e[0].elapsed_time(e[1]) * 1e3)
-    return min(out)
 
 
 def main():
@@ -135,20 +104,9 @@ def main():
              "voiced_share": float((f0 > 0).float().mean())}
 
     fns = {"yin": yin, "yin_cmnd": yin_cmnd, "extractor": extractor}
-    graphs = {k: graph_of(f) for k, f in fns.items()}
-    trash = torch.zeros(1 << 28, device=dev)
-    res_us = {k: [] for k in fns}
-    evi_us = {k: [] for k in fns}
     tdp = []
-    for _ in range(a.rounds):   # interleaved: drift of the machine hits every path alike
-        for k in fns:
-            res_us[k].append(time_graph(graphs[k]) * 1e6)
-            evi_us[k].append(evicted_us(fns[k], trash, 3))
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        torch_cmnd(padded, P.Lp, px.tau_max)
-        torch.cuda.synchronize()
-        tdp.append((time.perf_counter() - t0) * 1e6)
+    res_us, evi_us = timed_rounds(fns, a.rounds, torch.zeros(1 << 28, device=dev),
+                                  each_round=lambda: tdp.append(wall_us(lambda: torch_cmnd(padded, P.Lp, px.tau_max))))
     best = {k: min(v) for k, v in res_us.items()}
     pairs = B * T * 512 * 512                       # (lag, sample) pairs: one subtract and one fma each
     lane_ops = 2 * pairs

@@ -30,15 +30,11 @@ import statistics
 import sys
 import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "tools"))
-sys.path.insert(0, os.path.join(ROOT, "tests"))
-sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
-from gemm_ab import graph_of, time_graph  # noqa: E402
-from pitch_bench import evicted_us, speech_like  # noqa: E402
+from _bench import speech_like, timed_rounds, wall_us  # noqa: E402
 
 T = 800
 CLOCK_GHZ = 2.4
@@ -129,20 +125,9 @@ def main():
                      "frames_where_voicing_differs": float(((lag > 0) != plain.voiced).float().mean())}
             torch_args = (cm, lo, hi, tr.pos(), J, W, C)
 
-    graphs = {k: graph_of(f) for k, f in fns.items()}
-    trash = torch.zeros(1 << 28, device=dev)
-    res_us = {k: [] for k in fns}
-    evi_us = {k: [] for k in fns}
     tdp = []
-    for _ in range(a.rounds):   # interleaved: drift of the machine hits every path alike
-        for k in fns:
-            res_us[k].append(time_graph(graphs[k]) * 1e6)
-            evi_us[k].append(evicted_us(fns[k], trash, 3))
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        torch_track(*torch_args)
-        torch.cuda.synchronize()
-        tdp.append((time.perf_counter() - t0) * 1e6)
+    res_us, evi_us = timed_rounds(fns, a.rounds, torch.zeros(1 << 28, device=dev),
+                                  each_round=lambda: tdp.append(wall_us(lambda: torch_track(*torch_args))))
     best = {k: min(v) for k, v in res_us.items()}
     pairs = (T - 1) * S * S                          # per utterance: one subtract, one fma, one min each
     floor = 3 * pairs / (4 * 32 * CLOCK_GHZ * 1e3)   # us: one CU per utterance, 4 SIMDs of 32 lanes per clock

@@ -32,18 +32,13 @@ import os
 import statistics
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "tools"))
-sys.path.insert(0, os.path.join(ROOT, "tests"))
-sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import torch  # noqa: E402
 
-from gemm_ab import graph_of, time_graph  # noqa: E402
-from pitch_bench import evicted_us  # noqa: E402
+from _bench import HBM_GBPS, timed_rounds  # noqa: E402
 
 B, TX, N_OUT = 16, 128, 800
 SHAPES = [("bf16_512", torch.bfloat16, 512), ("f32_512", torch.float32, 512), ("f32_1", torch.float32, 1)]
-HBM_GBPS = 6290.0     # measured float4 copy rate of one MI355X (the guide's figure)
 
 
 def random_durations(seed=0):
@@ -73,18 +68,6 @@ def torch_repeat(h, d, n_out):
     rows = [torch.repeat_interleave(h[b], d[b].clamp(min=0).long(), dim=0) for b in range(h.shape[0])]
     y = torch.nn.utils.rnn.pad_sequence(rows, batch_first=True)
     return torch.nn.functional.pad(y, (0, 0, 0, n_out - y.shape[1]))
-
-
-def eager_us(fn, n=200):
-    fn()
-    torch.cuda.synchronize()
-    e = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
-    e[0].record()
-    for _ in range(n):
-        fn()
-    e[1].record()
-    torch.cuda.synchronize()
-    return e[0].elapsed_time(e[1]) * 1e3 / n
 
 
 def main():
@@ -175,18 +158,10 @@ def main():
         fns[f"bwd_one_utt_{nm}"] = tails[nm]
     kernel_legs = [k for k in fns if k.startswith(("plan", "fwd_", "bwd_", "gather_fwd_"))]
     eager_legs = [k for k in fns if k.startswith(("whole_", "gather_", "repeat_")) and not k.startswith("gather_fwd_")]
-    graphs = {k: graph_of(fns[k]) for k in kernel_legs}
-    res_us = {k: [] for k in kernel_legs}
-    eag_us = {k: [] for k in eager_legs}
-    evi_us = {k: [] for k in fns}
-    trash = torch.zeros(1 << 28, device=dev)
-    for _ in range(a.rounds):   # interleaved: drift of the machine hits every path alike
-        for k in fns:
-            if k in graphs:
-                res_us[k].append(time_graph(graphs[k]) * 1e6)
-            else:
-                eag_us[k].append(eager_us(fns[k]))
-            evi_us[k].append(evicted_us(fns[k], trash, 3))
+    assert set(kernel_legs) | set(eager_legs) == set(fns)
+    all_us, evi_us = timed_rounds(fns, a.rounds, torch.zeros(1 << 28, device=dev), eager=eager_legs, eager_runs=200)
+    res_us = {k: all_us[k] for k in kernel_legs}
+    eag_us = {k: all_us[k] for k in eager_legs}
     best = {k: min(v) for k, v in res_us.items()}
     eag = {k: min(v) for k, v in eag_us.items()}
     evi = {k: min(v) for k, v in evi_us.items()}

@@ -27,16 +27,12 @@ import statistics
 import sys
 import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "tools"))
-sys.path.insert(0, os.path.join(ROOT, "tests"))
-sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 import torch.nn.functional as F  # noqa: E402
 
-from gemm_ab import graph_of, time_graph  # noqa: E402
-from pitch_bench import evicted_us, speech_like  # noqa: E402
+from _bench import speech_like, timed_rounds  # noqa: E402
 
 B, N_OUT = 16, 204544
 PAIRS = [(48000, 22050), (44100, 22050)]
@@ -96,13 +92,7 @@ def bench_pair(sr_in, sr_out, rounds, trash):
              "resampler_equal_bits": bool(torch.equal(rs(wav, lens)[0], y)),
              "peak": float(y.abs().max())}
     fns = {"resample": resample, "resampler": resampler, "torch": torch_base}
-    graphs = {k: graph_of(f) for k, f in fns.items()}
-    res_us = {k: [] for k in fns}
-    evi_us = {k: [] for k in fns}
-    for _ in range(rounds):   # interleaved: drift of the machine hits every path alike
-        for k in fns:
-            res_us[k].append(time_graph(graphs[k]) * 1e6)
-            evi_us[k].append(evicted_us(fns[k], trash, 3))
+    res_us, evi_us = timed_rounds(fns, rounds, trash)
     best = {k: min(v) for k, v in res_us.items()}
     evi = {k: min(v) for k, v in evi_us.items()}
     nbytes = 4 * B * (L + N_OUT)

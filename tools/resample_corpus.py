@@ -10,26 +10,21 @@ samples the PCM16 range clipped.  --out is then a corpus every other tool here r
     python tools/resample_corpus.py --in /data/VCTK-lj --out /data/VCTK-22k --sr-in 48000 \
         [--sr 22050] [--zeros 24] [--rolloff 0.9] [--beta 10.0] [--batch 16]
 """
-import argparse
 import json
 import os
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "transformer-tacotron2_amd"))
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import _corpus_cli as cli  # noqa: E402
 
 
 def parse_args(argv=None):
-    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("--in", dest="src", required=True, help="corpus root (metadata.csv, wavs/) at --sr-in")
-    ap.add_argument("--out", required=True, help="root of the resampled corpus")
-    ap.add_argument("--sr-in", type=int, required=True, help="sample rate of the corpus' files")
-    ap.add_argument("--sr", type=int, default=22050, help="sample rate to write")
-    ap.add_argument("--zeros", type=int, default=24, help="zero crossings of the sinc either side")
-    ap.add_argument("--rolloff", type=float, default=0.9, help="cutoff as a fraction of the lower Nyquist")
-    ap.add_argument("--beta", type=float, default=10.0, help="Kaiser window shape")
-    ap.add_argument("--batch", type=int, default=16)
-    return ap.parse_args(argv)
+    def own(ap):
+        ap.add_argument("--sr", type=int, default=22050, help="sample rate to write")
+        ap.add_argument("--zeros", type=int, default=24, help="zero crossings of the sinc either side")
+        ap.add_argument("--rolloff", type=float, default=0.9, help="cutoff as a fraction of the lower Nyquist")
+        ap.add_argument("--beta", type=float, default=10.0, help="Kaiser window shape")
+    return cli.parse_args(__doc__, "resampled", argv, own, sr_in=None)
 
 
 def main(argv=None):
@@ -37,9 +32,8 @@ def main(argv=None):
     from tt2.audio import Resampler
     from tt2.data import LJSpeech, resample_corpus
 
-    ds = LJSpeech(a.src, sr=a.sr_in)
     rs = Resampler(a.sr_in, a.sr, zeros=a.zeros, rolloff=a.rolloff, beta=a.beta)
-    man = resample_corpus(ds, a.out, rs, batch_size=a.batch)
+    man = resample_corpus(LJSpeech(a.src, sr=a.sr_in), a.out, rs, batch_size=a.batch)
     utts = man["utterances"].values()
     print(json.dumps({"out": a.out, "utterances": len(utts), "resampler": man["resampler"],
                       "samples_out": sum(u["samples_out"] for u in utts), "clipped": sum(u["clipped"] for u in utts)}))

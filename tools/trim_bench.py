@@ -29,19 +29,14 @@ import statistics
 import sys
 import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "tools"))
-sys.path.insert(0, os.path.join(ROOT, "tests"))
-sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 import torch.nn.functional as F  # noqa: E402
 
-from gemm_ab import graph_of, time_graph  # noqa: E402
-from pitch_bench import evicted_us, speech_like  # noqa: E402
+from _bench import HBM_GBPS, speech_like, timed_rounds  # noqa: E402
 
 B, N, SR = 16, 204544, 22050
-HBM_GBPS = 6290.0     # measured float4 copy rate of one MI355X (the guide's figure)
 
 
 def padded_speech():
@@ -119,14 +114,7 @@ def main():
              "trimmer_equal_bits": bool(torch.equal(t.audio, y) and torch.equal(t.lens, ol) and torch.equal(t.start, st)),
              "start": [int(st.min()), int(st.max())], "out_lens": [int(ol.min()), int(ol.max())]}
     fns = {"trim": trim, "trimmer": trimmer, "torch": torch_base}
-    graphs = {k: graph_of(f) for k, f in fns.items()}
-    res_us = {k: [] for k in fns}
-    evi_us = {k: [] for k in fns}
-    trash = torch.zeros(1 << 28, device=dev)
-    for _ in range(a.rounds):   # interleaved: drift of the machine hits every path alike
-        for k in fns:
-            res_us[k].append(time_graph(graphs[k]) * 1e6)
-            evi_us[k].append(evicted_us(fns[k], trash, 3))
+    res_us, evi_us = timed_rounds(fns, a.rounds, torch.zeros(1 << 28, device=dev))
     best = {k: min(v) for k, v in res_us.items()}
     evi = {k: min(v) for k, v in evi_us.items()}
     nbytes = 4 * (int(lens.sum()) + B * N)

@@ -122,30 +122,42 @@ class MelExtractor:
             self.plans[key] = _Plan(B, L, self.dev)
         return self.plans[key]
 
+    def _reflect_pad(self, x: torch.Tensor, lens: torch.Tensor | None, P: _Plan):
+        check(lib().tt2_reflect_pad(x.data_ptr(), x.stride(0), ptr(lens), P.B, P.L, P.padded.data_ptr(), P.Lp,
+                                    N_FFT // 2, stream_ptr()), "tt2_reflect_pad")
+
+    def _dft(self, P: _Plan):
+        ops.gemm(P.padded, self.basis, P.spec, P.M, LD_SPEC, N_FFT, HOP, N_FFT, LD_SPEC)
+
     def stft(self, x: torch.Tensor, lens: torch.Tensor | None, P: _Plan):
         """P.spec rows [b * R + f] = [Re | Im] STFT of utterance b's frame f (f32)."""
-        L = lib()
-        check(L.tt2_reflect_pad(x.data_ptr(), x.stride(0), ptr(lens), P.B, P.L, P.padded.data_ptr(), P.Lp,
-                                N_FFT // 2, stream_ptr()), "tt2_reflect_pad")
-        ops.gemm(P.padded, self.basis, P.spec, P.M, LD_SPEC, N_FFT, HOP, N_FFT, LD_SPEC)
+        self._reflect_pad(x, lens, P)
+        self._dft(P)
+
+    def _padded(self, audio: torch.Tensor, lens: torch.Tensor | None):
+        """Reflect-pad audio [B, L] into its plan's buffer -> (P, lens as int32 on the device or None,
+        frames [B] int32 = 1 + lens // 256, or P.T without lens): the grid of the mel and pitch features."""
+        B, Lx = audio.shape
+        audio = audio.to(self.dev, torch.float32).contiguous()
+        P = self.plan(B, Lx)
+        lens32 = lens.to(self.dev, torch.int32) if lens is not None else None
+        self._reflect_pad(audio, lens32, P)
+        frames = (1 + lens32 // HOP) if lens32 is not None else torch.full((B,), P.T, dtype=torch.int32,
+                                                                              device=self.dev)
+        return P, lens32, frames
 
     def __call__(self, audio: torch.Tensor, lens: torch.Tensor | None = None):
         """audio [B, L] f32 (device), lens [B] samples (optional, each > 512).
         Returns (log-mel [B, T, 80] f32, frames [B] int32) with T = 1 + L // 256;
         frames past an utterance's own 1 + len // 256 hold log(1e-5) (silence)."""
-        B, Lx = audio.shape
-        audio = audio.to(self.dev, torch.float32).contiguous()
-        P = self.plan(B, Lx)
-        lens32 = lens.to(self.dev, torch.int32) if lens is not None else None
-        self.stft(audio, lens32, P)
+        P, _, frames = self._padded(audio, lens)
+        self._dft(P)
         L = lib()
         check(L.tt2_spec_magnitude(P.spec.data_ptr(), LD_SPEC, P.M, NB, P.mag.data_ptr(), LD_MAG, stream_ptr()),
               "tt2_spec_magnitude")
         ops.gemm(P.mag, self.fb, P.rows, P.M, N_MELS, LD_MAG, LD_MAG, LD_MAG, N_MELS)
-        frames = (1 + lens32 // HOP) if lens32 is not None else torch.full((B,), P.T, dtype=torch.int32,
-                                                                              device=self.dev)
-        mel = torch.empty(B, P.T, N_MELS, dtype=torch.float32, device=self.dev)
-        check(L.tt2_mel_rows(P.rows.data_ptr(), N_MELS, mel.data_ptr(), frames.data_ptr(), B, P.T, N_MELS, P.R,
+        mel = torch.empty(P.B, P.T, N_MELS, dtype=torch.float32, device=self.dev)
+        check(L.tt2_mel_rows(P.rows.data_ptr(), N_MELS, mel.data_ptr(), frames.data_ptr(), P.B, P.T, N_MELS, P.R,
                              LOG_CLAMP, 0, stream_ptr()), "tt2_mel_rows")
         return mel, frames
 
@@ -245,14 +257,8 @@ class PitchExtractor:
     def _yin(self, audio, lens, want_cmnd: bool):
         """The pad and the tt2_yin launch -> (f0, lag, aper, energy, frames, cmnd or None), fresh
         tensors; cmnd [B, T, tau_max + 1] is d'(0 .. tau_max) of every valid frame (PitchTracker)."""
-        B, Lx = audio.shape
-        dev = self.mx.dev
-        audio = audio.to(dev, torch.float32).contiguous()
-        P = self.mx.plan(B, Lx)
-        lens32 = lens.to(dev, torch.int32) if lens is not None else None
-        check(lib().tt2_reflect_pad(audio.data_ptr(), audio.stride(0), ptr(lens32), P.B, P.L, P.padded.data_ptr(),
-                                    P.Lp, N_FFT // 2, stream_ptr()), "tt2_reflect_pad")
-        frames = (1 + lens32 // HOP) if lens32 is not None else torch.full((B,), P.T, dtype=torch.int32, device=dev)
+        P, _, frames = self.mx._padded(audio, lens)
+        B, dev = P.B, self.mx.dev
         f0 = torch.empty(B, P.T, dtype=torch.float32, device=dev)
         lag = torch.empty(B, P.T, dtype=torch.int32, device=dev)
         aper, energy = torch.empty_like(f0), torch.empty_like(f0)
@@ -365,7 +371,45 @@ def resample_bank(sr_in: int, sr_out: int, zeros: int = 24, rolloff: float = 0.9
     return ResampleBank(up, down, half, taps)
 
 
-class Resampler:
+class _Stage:
+    """What the waveform stages (Resampler, SilenceTrimmer, LoudnessNormalizer) do to their input."""
+    resampler = None             # the stage run first: anything of the resampler protocol
+
+    def _prepare(self, audio, lens):
+        """The front stage's output (or the input) as the kernels take it: audio f32 on the device with
+        a contiguous last dim (row views stay views), lens a contiguous int32 [B] or None."""
+        if self.resampler is not None:
+            audio, lens = self.resampler(audio, lens)
+        audio = audio.to(self.dev, torch.float32)
+        if audio.stride(1) != 1 and audio.shape[1] > 1:
+            audio = audio.contiguous()
+        lens32 = lens.to(self.dev, torch.int32).contiguous() if lens is not None else None
+        return audio, lens32
+
+
+class _Chained(_Stage):
+    """A stage that works at one rate `sr` and may run another (resampler=) in front of itself, so that
+    one object takes a batch from the corpus's rate to this stage's output.  A subclass calls _chain
+    from its constructor and gives its own parameters in _params."""
+
+    def _chain(self, resampler, sr, device):
+        if resampler is not None and int(resampler.sr_out) != int(sr):
+            raise ValueError(f"{type(self).__name__}: the resampler writes {resampler.sr_out} Hz, "
+                             f"this stage works at {sr} Hz")
+        self.sr, self.resampler, self.dev = int(sr), resampler, torch.device(device)
+        self._ws = ops.Workspace()
+
+    sr_in = property(lambda self: self.resampler.sr_in if self.resampler is not None else self.sr)
+    sr_out = property(lambda self: self.sr)
+
+    def params(self) -> dict:
+        p = self._params()
+        if self.resampler is not None:
+            p["resampler"] = self.resampler.params()
+        return p
+
+
+class Resampler(_Stage):
     """Sample-rate conversion sr_in -> sr_out (tt2_resample; include/tt2_capi.h has the definition)
     of a padded batch, with the bank of resample_bank rounded once to f32.  The corpus tool
     (tools/resample_corpus.py) and data.collate(resampler=) run it; MelExtractor, PitchExtractor
@@ -407,10 +451,7 @@ class Resampler:
             if lens is None:
                 lens = torch.full((B,), L, dtype=torch.int32, device=audio.device)
             return audio, lens
-        audio = audio.to(self.dev, torch.float32)
-        if audio.stride(1) != 1 and L > 1:
-            audio = audio.contiguous()
-        lens32 = lens.to(self.dev, torch.int32).contiguous() if lens is not None else None
+        audio, lens32 = self._prepare(audio, lens)
         n_out = self.out_len(L)
         if B == 0 or n_out == 0:
             return (torch.zeros(B, n_out, dtype=torch.float32, device=self.dev),
@@ -430,7 +471,7 @@ class Trimmed(NamedTuple):
     energy: torch.Tensor | None
 
 
-class SilenceTrimmer:
+class SilenceTrimmer(_Chained):
     """Leading / trailing silence trimming of a padded batch (tt2_trim; include/tt2_capi.h has the
     definition): everything before the first and after the last frame whose energy is within top_db
     of the utterance's loudest frame goes, `keep` samples either side stay, interior silence stays.
@@ -454,37 +495,22 @@ class SilenceTrimmer:
                              f"got frame {frame}, hop {hop}")
         if int(keep) != keep or keep < 0:
             raise ValueError(f"SilenceTrimmer: keep must be an integer >= 0, got {keep}")
-        if resampler is not None and int(resampler.sr_out) != int(sr):
-            raise ValueError(f"SilenceTrimmer: the resampler writes {resampler.sr_out} Hz, the trimmer works at {sr} Hz")
-        self.top_db, self.frame, self.hop, self.keep, self.sr = top_db, int(frame), int(hop), int(keep), int(sr)
+        self._chain(resampler, sr, device)
+        self.top_db, self.frame, self.hop, self.keep = top_db, int(frame), int(hop), int(keep)
         self.r = self.frame // (2 * self.hop)
         # the power ratio in float64, rounded once to f32 (the C argument is an f32)
         self.ratio = float(torch.tensor(10.0 ** (-top_db / 10.0), dtype=torch.float64).float())
-        self.resampler = resampler
-        self.dev = torch.device(device)
-        self._ws = ops.Workspace()
 
-    sr_in = property(lambda self: self.resampler.sr_in if self.resampler is not None else self.sr)
-    sr_out = property(lambda self: self.sr)
-
-    def params(self) -> dict:
-        p = {"top_db": self.top_db, "frame": self.frame, "hop": self.hop, "r": self.r, "keep": self.keep,
-             "ratio": self.ratio, "sr": self.sr}
-        if self.resampler is not None:
-            p["resampler"] = self.resampler.params()
-        return p
+    def _params(self) -> dict:
+        return {"top_db": self.top_db, "frame": self.frame, "hop": self.hop, "r": self.r, "keep": self.keep,
+                "ratio": self.ratio, "sr": self.sr}
 
     def trim(self, audio: torch.Tensor, lens: torch.Tensor | None = None, want_energy: bool = False) -> Trimmed:
         """audio [B, L] f32 at sr_in, lens [B] samples (optional) -> Trimmed, every field a fresh
         tensor; the scratch is this object's own, grown on demand.  On the current stream, no host
         synchronisation."""
-        if self.resampler is not None:
-            audio, lens = self.resampler(audio, lens)
-        audio = audio.to(self.dev, torch.float32)
+        audio, lens32 = self._prepare(audio, lens)
         B, L = audio.shape
-        if audio.stride(1) != 1 and L > 1:
-            audio = audio.contiguous()
-        lens32 = lens.to(self.dev, torch.int32).contiguous() if lens is not None else None
         energy = torch.zeros(B, L // self.hop + 1, dtype=torch.float32, device=self.dev) if want_energy else None
         if B == 0 or L == 0:
             z = torch.zeros(B, dtype=torch.int32, device=self.dev)
@@ -543,7 +569,7 @@ class Normalized(NamedTuple):
     limited: torch.Tensor
 
 
-class LoudnessNormalizer:
+class LoudnessNormalizer(_Chained):
     """Loudness normalisation of a padded batch (tt2_loudness; include/tt2_capi.h has the definition):
     integrated loudness per ITU-R BS.1770-4 (K-weighting, 400 ms blocks every 100 ms, the -70 LKFS
     absolute and the -10 LU relative gate), one gain per utterance that brings it to `target` LKFS
@@ -561,10 +587,8 @@ class LoudnessNormalizer:
             raise ValueError(f"LoudnessNormalizer: target and peak_db must be finite, got {target}, {peak_db}")
         if int(sr) != sr or sr < 10 or sr % 10:
             raise ValueError(f"LoudnessNormalizer: the rate must be a positive multiple of 10 (100 ms steps), got {sr}")
-        if resampler is not None and int(resampler.sr_out) != int(sr):
-            raise ValueError(f"LoudnessNormalizer: the resampler writes {resampler.sr_out} Hz, the normaliser "
-                             f"works at {sr} Hz")
-        self.target, self.peak_db, self.sr = target, peak_db, int(sr)
+        self._chain(resampler, sr, device)
+        self.target, self.peak_db = target, peak_db
         self.step = self.sr // 10
         (b1, a1), (b2, a2) = kweighting(self.sr)
         self.coef = (*b1, a1[1], a1[2], *b2, a2[1], a2[2])
@@ -573,28 +597,11 @@ class LoudnessNormalizer:
         self.target_ms = 10.0 ** ((target + 0.691) / 10.0)
         # the amplitude ratio in float64, rounded once to f32 (the C argument is an f32)
         self.ceiling = float(torch.tensor(10.0 ** (peak_db / 20.0), dtype=torch.float64).float())
-        self.resampler = resampler
-        self.dev = torch.device(device)
-        self._ws = ops.Workspace()
 
-    sr_in = property(lambda self: self.resampler.sr_in if self.resampler is not None else self.sr)
-    sr_out = property(lambda self: self.sr)
-
-    def params(self) -> dict:
-        p = {"target": self.target, "peak_db": self.peak_db, "sr": self.sr, "step": self.step, "coef": list(self.coef),
-             "abs_sum": self.abs_sum, "rel_ratio": self.rel_ratio, "target_ms": self.target_ms, "ceiling": self.ceiling}
-        if self.resampler is not None:
-            p["resampler"] = self.resampler.params()
-        return p
-
-    def _prepare(self, audio, lens):
-        if self.resampler is not None:
-            audio, lens = self.resampler(audio, lens)
-        audio = audio.to(self.dev, torch.float32)
-        if audio.stride(1) != 1 and audio.shape[1] > 1:
-            audio = audio.contiguous()
-        lens32 = lens.to(self.dev, torch.int32).contiguous() if lens is not None else None
-        return audio, lens32
+    def _params(self) -> dict:
+        return {"target": self.target, "peak_db": self.peak_db, "sr": self.sr, "step": self.step,
+                "coef": list(self.coef), "abs_sum": self.abs_sum, "rel_ratio": self.rel_ratio,
+                "target_ms": self.target_ms, "ceiling": self.ceiling}
 
     def _run(self, audio, lens32, **out):
         ops.loudness(audio, self.step, self.coef, self.abs_sum, self.rel_ratio, self.target_ms, self.ceiling,

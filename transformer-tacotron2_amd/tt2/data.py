@@ -133,6 +133,15 @@ def bucket_batches(lengths, batch_size: int, bucket_mult: int = 8, seed: int = 0
     return batches
 
 
+def pad_batch(wavs):
+    """(audio [B, L] f32, lens [B] int32) on the host: the waveforms (1-D float32 arrays) as rows,
+    zero-padded to the longest."""
+    audio = torch.zeros(len(wavs), max(len(w) for w in wavs), dtype=torch.float32)
+    for b, w in enumerate(wavs):
+        audio[b, :len(w)] = torch.from_numpy(w)
+    return audio, torch.tensor([len(w) for w in wavs], dtype=torch.int32)
+
+
 def collate(ds: LJSpeech, indices, extractor, device="cuda", resampler=None):
     """(text [B, Tx] i64, text_len [B], mel [B, T, 80] f32, mel_len [B]) for one batch;
     the log-mels come from one batched GPU STFT (tt2.audio.MelExtractor).  With a resampler (a
@@ -149,12 +158,7 @@ def collate(ds: LJSpeech, indices, extractor, device="cuda", resampler=None):
     for b, s in enumerate(ids):
         text[b, :len(s)] = torch.tensor(s)
     text_len = torch.tensor([len(s) for s in ids])
-    L = max(len(w) for w in wavs)
-    audio = torch.zeros(B, L, dtype=torch.float32)
-    for b, w in enumerate(wavs):
-        audio[b, :len(w)] = torch.from_numpy(w)
-    lens = torch.tensor([len(w) for w in wavs], dtype=torch.int32)
-    audio, lens = audio.to(device), lens.to(device)
+    audio, lens = (t.to(device) for t in pad_batch(wavs))
     if resampler is not None:
         audio, lens = resampler(audio, lens)
     mel, frames = extractor(audio, lens)
@@ -300,6 +304,68 @@ def extract_pitch(batches, out_dir: str, extractor, durations_dir: str | None = 
     return manifest
 
 
+def _numbers(t, kind=int):
+    return [kind(v) for v in torch.as_tensor(t).cpu()]
+
+
+def _corpus_pass(who, ds, out_root, stage, batch_size, run, entry, key, manifest_name, skip_empty=True, totals=None):
+    """One pass of a waveform stage over the corpus `ds` into a corpus of the same layout under
+    out_root; what resample_corpus, trim_corpus and normalize_corpus share.  Per batch of batch_size
+    utterances in corpus order: run(audio [B, L], lens [B]) -> (audio_out, out_lens, extras), extras a
+    tuple of per-utterance lists; per utterance: out_root/wavs/<id>.wav (PCM16 mono at stage.sr_out:
+    rint(x * 32768) clipped to [-32768, 32767]) and entry(uid, samples_in, samples_out, clipped,
+    *its extras) -> its manifest entry.  With skip_empty an utterance of no samples is not written,
+    is listed under "empty", and its line is left out of the copied metadata.csv.  totals() -> the
+    corpus-level keys.  Writes out_root/<manifest_name>: {key: stage.params(), "utterances": ...}
+    and returns it."""
+    import shutil
+    from scipy.io import wavfile
+    sr = getattr(ds, "sr", 22050)
+    if int(stage.sr_in) != int(sr):
+        raise ValueError(f"{who}: the stage reads {stage.sr_in} Hz, the corpus is at {sr} Hz")
+    if batch_size < 1:
+        raise ValueError(f"{who}: batch_size must be at least 1")
+    if os.path.abspath(out_root) == os.path.abspath(ds.root):
+        raise ValueError(f"{who}: out_root is the corpus itself")
+    os.makedirs(os.path.join(out_root, "wavs"), exist_ok=True)
+    dev = getattr(stage, "dev", "cpu")
+    manifest = {key: stage.params() if hasattr(stage, "params") else {}, "utterances": {}}
+    empty = []
+    if skip_empty:
+        manifest["empty"] = empty
+    for s in range(0, len(ds), batch_size):
+        idx = list(range(s, min(s + batch_size, len(ds))))
+        wavs = [ds.wav(i) for i in idx]
+        audio, lens = pad_batch(wavs)
+        y, out_lens, extras = run(audio.to(dev), lens.to(dev))
+        y = torch.as_tensor(y).detach().float().cpu().numpy()
+        out_lens = _numbers(out_lens)
+        for b, i in enumerate(idx):
+            uid = str(ds.items[i][0])
+            q = np.rint(y[b, :out_lens[b]].astype(np.float64) * 32768.0)
+            clipped = int(((q < -32768) | (q > 32767)).sum())
+            manifest["utterances"][uid] = entry(uid, len(wavs[b]), out_lens[b], clipped, *(e[b] for e in extras))
+            if skip_empty and out_lens[b] == 0:
+                empty.append(uid)
+                continue
+            wavfile.write(os.path.join(out_root, "wavs", uid + ".wav"), int(stage.sr_out),
+                          np.clip(q, -32768, 32767).astype(np.int16))
+    if totals is not None:
+        manifest.update(totals())
+    src, dst = os.path.join(ds.root, "metadata.csv"), os.path.join(out_root, "metadata.csv")
+    if not empty:
+        shutil.copyfile(src, dst)
+    else:
+        gone = set(empty)
+        with open(src, encoding="utf-8", newline="") as f, open(dst, "w", encoding="utf-8", newline="") as g:
+            for line in f:
+                if line.split("|", 1)[0].rstrip("\r\n") not in gone:
+                    g.write(line)
+    with open(os.path.join(out_root, manifest_name), "w") as f:
+        json.dump(manifest, f, indent=1, sort_keys=True)
+    return manifest
+
+
 def resample_corpus(ds: LJSpeech, out_root: str, resampler, batch_size: int = 16):
     """The corpus `ds` at the resampler's output rate, as a corpus of the same layout under
     out_root: out_root/wavs/<id>.wav (PCM16 mono at sr_out: rint(x * 32768) clipped to
@@ -308,40 +374,12 @@ def resample_corpus(ds: LJSpeech, out_root: str, resampler, batch_size: int = 16
     number of samples the PCM16 range cut.  `resampler` is a tt2.audio.Resampler whose sr_in is
     ds.sr, or any callable (audio [B, L], lens [B]) -> (audio_out, out_lens) with sr_in, sr_out and
     params(): one call per batch of batch_size utterances in corpus order.  Returns the manifest."""
-    import shutil
-    from scipy.io import wavfile
-    if int(resampler.sr_in) != int(getattr(ds, "sr", 22050)):
-        raise ValueError(f"resample_corpus: the resampler reads {resampler.sr_in} Hz, the corpus is at "
-                         f"{getattr(ds, 'sr', 22050)} Hz")
-    if batch_size < 1:
-        raise ValueError("resample_corpus: batch_size must be at least 1")
-    if os.path.abspath(out_root) == os.path.abspath(ds.root):
-        raise ValueError("resample_corpus: out_root is the corpus itself")
-    os.makedirs(os.path.join(out_root, "wavs"), exist_ok=True)
-    dev = getattr(resampler, "dev", "cpu")
-    manifest = {"resampler": resampler.params() if hasattr(resampler, "params") else {}, "utterances": {}}
-    for s in range(0, len(ds), batch_size):
-        idx = list(range(s, min(s + batch_size, len(ds))))
-        wavs = [ds.wav(i) for i in idx]
-        audio = torch.zeros(len(idx), max(len(w) for w in wavs), dtype=torch.float32)
-        for b, w in enumerate(wavs):
-            audio[b, :len(w)] = torch.from_numpy(w)
-        lens = torch.tensor([len(w) for w in wavs], dtype=torch.int32)
-        y, out_lens = resampler(audio.to(dev), lens.to(dev))
-        y = y.detach().float().cpu().numpy()
-        out_lens = [int(n) for n in torch.as_tensor(out_lens).cpu()]
-        for b, i in enumerate(idx):
-            uid = ds.items[i][0]
-            q = np.rint(y[b, :out_lens[b]].astype(np.float64) * 32768.0)
-            clipped = int(((q < -32768) | (q > 32767)).sum())
-            wavfile.write(os.path.join(out_root, "wavs", uid + ".wav"), int(resampler.sr_out),
-                          np.clip(q, -32768, 32767).astype(np.int16))
-            manifest["utterances"][str(uid)] = {"samples_in": len(wavs[b]), "samples_out": out_lens[b],
-                                                "clipped": clipped}
-    shutil.copyfile(os.path.join(ds.root, "metadata.csv"), os.path.join(out_root, "metadata.csv"))
-    with open(os.path.join(out_root, "resample.json"), "w") as f:
-        json.dump(manifest, f, indent=1, sort_keys=True)
-    return manifest
+    def entry(uid, samples_in, samples_out, clipped):
+        return {"samples_in": samples_in, "samples_out": samples_out, "clipped": clipped}
+
+    return _corpus_pass("resample_corpus", ds, out_root, resampler, batch_size,
+                        lambda audio, lens: (*resampler(audio, lens), ()), entry, "resampler", "resample.json",
+                        skip_empty=False)
 
 
 def trim_corpus(ds: LJSpeech, out_root: str, trimmer, batch_size: int = 16):
@@ -356,56 +394,18 @@ def trim_corpus(ds: LJSpeech, out_root: str, trimmer, batch_size: int = 16):
     zero-length file.  `trimmer` is a tt2.audio.SilenceTrimmer whose sr_in is ds.sr, or any object
     with sr_in, sr_out, params() and trim(audio [B, L], lens [B]) -> (audio, lens, start, energy):
     one call per batch of batch_size utterances in corpus order.  Returns the manifest."""
-    import shutil
-    from scipy.io import wavfile
-    if int(trimmer.sr_in) != int(getattr(ds, "sr", 22050)):
-        raise ValueError(f"trim_corpus: the trimmer reads {trimmer.sr_in} Hz, the corpus is at "
-                         f"{getattr(ds, 'sr', 22050)} Hz")
-    if batch_size < 1:
-        raise ValueError("trim_corpus: batch_size must be at least 1")
-    if os.path.abspath(out_root) == os.path.abspath(ds.root):
-        raise ValueError("trim_corpus: out_root is the corpus itself")
-    os.makedirs(os.path.join(out_root, "wavs"), exist_ok=True)
-    dev = getattr(trimmer, "dev", "cpu")
-    sr_in, sr_out = int(trimmer.sr_in), int(trimmer.sr_out)
-    manifest = {"trimmer": trimmer.params() if hasattr(trimmer, "params") else {}, "utterances": {}, "empty": []}
-    removed = 0.0
-    for s in range(0, len(ds), batch_size):
-        idx = list(range(s, min(s + batch_size, len(ds))))
-        wavs = [ds.wav(i) for i in idx]
-        audio = torch.zeros(len(idx), max(len(w) for w in wavs), dtype=torch.float32)
-        for b, w in enumerate(wavs):
-            audio[b, :len(w)] = torch.from_numpy(w)
-        lens = torch.tensor([len(w) for w in wavs], dtype=torch.int32)
-        y, out_lens, start = trimmer.trim(audio.to(dev), lens.to(dev))[:3]
-        y = torch.as_tensor(y).detach().float().cpu().numpy()
-        out_lens = [int(n) for n in torch.as_tensor(out_lens).cpu()]
-        start = [int(n) for n in torch.as_tensor(start).cpu()]
-        for b, i in enumerate(idx):
-            uid = str(ds.items[i][0])
-            q = np.rint(y[b, :out_lens[b]].astype(np.float64) * 32768.0)
-            clipped = int(((q < -32768) | (q > 32767)).sum())
-            manifest["utterances"][uid] = {"samples_in": len(wavs[b]), "start": start[b],
-                                           "samples_out": out_lens[b], "clipped": clipped}
-            removed += len(wavs[b]) / sr_in - out_lens[b] / sr_out
-            if out_lens[b] == 0:
-                manifest["empty"].append(uid)
-                continue
-            wavfile.write(os.path.join(out_root, "wavs", uid + ".wav"), sr_out,
-                          np.clip(q, -32768, 32767).astype(np.int16))
-    manifest["removed_seconds"] = removed
-    src, dst = os.path.join(ds.root, "metadata.csv"), os.path.join(out_root, "metadata.csv")
-    if not manifest["empty"]:
-        shutil.copyfile(src, dst)
-    else:
-        gone = set(manifest["empty"])
-        with open(src, encoding="utf-8", newline="") as f, open(dst, "w", encoding="utf-8", newline="") as g:
-            for line in f:
-                if line.split("|", 1)[0].rstrip("\r\n") not in gone:
-                    g.write(line)
-    with open(os.path.join(out_root, "trim.json"), "w") as f:
-        json.dump(manifest, f, indent=1, sort_keys=True)
-    return manifest
+    sr_in, sr_out, removed = int(trimmer.sr_in), int(trimmer.sr_out), [0.0]
+
+    def run(audio, lens):
+        y, out_lens, start = trimmer.trim(audio, lens)[:3]
+        return y, out_lens, (_numbers(start),)
+
+    def entry(uid, samples_in, samples_out, clipped, start):
+        removed[0] += samples_in / sr_in - samples_out / sr_out
+        return {"samples_in": samples_in, "start": start, "samples_out": samples_out, "clipped": clipped}
+
+    return _corpus_pass("trim_corpus", ds, out_root, trimmer, batch_size, run, entry, "trimmer", "trim.json",
+                        totals=lambda: {"removed_seconds": removed[0]})
 
 
 def normalize_corpus(ds: LJSpeech, out_root: str, normalizer, batch_size: int = 16):
@@ -424,63 +424,29 @@ def normalize_corpus(ds: LJSpeech, out_root: str, normalizer, batch_size: int = 
     normalize(audio [B, L], lens [B]) -> (audio, lens, loud, gain, peak, limited): one call per batch
     of batch_size utterances in corpus order.  Returns the manifest."""
     import math
-    import shutil
-    from scipy.io import wavfile
-    if int(normalizer.sr_in) != int(getattr(ds, "sr", 22050)):
-        raise ValueError(f"normalize_corpus: the normaliser reads {normalizer.sr_in} Hz, the corpus is at "
-                         f"{getattr(ds, 'sr', 22050)} Hz")
-    if batch_size < 1:
-        raise ValueError("normalize_corpus: batch_size must be at least 1")
-    if os.path.abspath(out_root) == os.path.abspath(ds.root):
-        raise ValueError("normalize_corpus: out_root is the corpus itself")
-    os.makedirs(os.path.join(out_root, "wavs"), exist_ok=True)
-    dev = getattr(normalizer, "dev", "cpu")
-    manifest = {"normalizer": normalizer.params() if hasattr(normalizer, "params") else {}, "utterances": {},
-                "unmeasured": [], "empty": []}
-    measured, n_limited = [], 0
-    for s in range(0, len(ds), batch_size):
-        idx = list(range(s, min(s + batch_size, len(ds))))
-        wavs = [ds.wav(i) for i in idx]
-        audio = torch.zeros(len(idx), max(len(w) for w in wavs), dtype=torch.float32)
-        for b, w in enumerate(wavs):
-            audio[b, :len(w)] = torch.from_numpy(w)
-        lens = torch.tensor([len(w) for w in wavs], dtype=torch.int32)
-        y, out_lens, loud, gain, peak, limited = normalizer.normalize(audio.to(dev), lens.to(dev))[:6]
-        y = torch.as_tensor(y).detach().float().cpu().numpy()
-        out_lens = [int(n) for n in torch.as_tensor(out_lens).cpu()]
-        loud, gain, peak = ([float(v) for v in torch.as_tensor(t).cpu()] for t in (loud, gain, peak))
-        limited = [int(v) for v in torch.as_tensor(limited).cpu()]
-        for b, i in enumerate(idx):
-            uid = str(ds.items[i][0])
-            q = np.rint(y[b, :out_lens[b]].astype(np.float64) * 32768.0)
-            clipped = int(((q < -32768) | (q > 32767)).sum())
-            ok = math.isfinite(loud[b])
-            manifest["utterances"][uid] = {"samples": out_lens[b], "loudness_in": loud[b] if ok else None,
-                                           "gain_db": 20.0 * math.log10(gain[b]) if gain[b] > 0 else None,
-                                           "peak_in": peak[b], "limited": bool(limited[b]), "clipped": clipped}
-            if ok:
-                measured.append(loud[b])
-                n_limited += limited[b]
-            else:
-                manifest["unmeasured"].append(uid)
-            if out_lens[b] == 0:
-                manifest["empty"].append(uid)
-                continue
-            wavfile.write(os.path.join(out_root, "wavs", uid + ".wav"), int(normalizer.sr_out),
-                          np.clip(q, -32768, 32767).astype(np.int16))
-    manifest["stats"] = {"measured": len(measured), "limited": n_limited,
-                         "mean_loudness_in": sum(measured) / len(measured) if measured else None,
-                         "min_loudness_in": min(measured) if measured else None,
-                         "max_loudness_in": max(measured) if measured else None}
-    src, dst = os.path.join(ds.root, "metadata.csv"), os.path.join(out_root, "metadata.csv")
-    if not manifest["empty"]:
-        shutil.copyfile(src, dst)
-    else:
-        gone = set(manifest["empty"])
-        with open(src, encoding="utf-8", newline="") as f, open(dst, "w", encoding="utf-8", newline="") as g:
-            for line in f:
-                if line.split("|", 1)[0].rstrip("\r\n") not in gone:
-                    g.write(line)
-    with open(os.path.join(out_root, "loudness.json"), "w") as f:
-        json.dump(manifest, f, indent=1, sort_keys=True)
-    return manifest
+    measured, n_limited, unmeasured = [], [0], []
+
+    def run(audio, lens):
+        y, out_lens, loud, gain, peak, limited = normalizer.normalize(audio, lens)[:6]
+        return y, out_lens, (_numbers(loud, float), _numbers(gain, float), _numbers(peak, float), _numbers(limited))
+
+    def entry(uid, samples_in, samples_out, clipped, loud, gain, peak, limited):
+        ok = math.isfinite(loud)
+        if ok:
+            measured.append(loud)
+            n_limited[0] += limited
+        else:
+            unmeasured.append(uid)
+        return {"samples": samples_out, "loudness_in": loud if ok else None,
+                "gain_db": 20.0 * math.log10(gain) if gain > 0 else None,
+                "peak_in": peak, "limited": bool(limited), "clipped": clipped}
+
+    def totals():
+        return {"unmeasured": unmeasured,
+                "stats": {"measured": len(measured), "limited": n_limited[0],
+                          "mean_loudness_in": sum(measured) / len(measured) if measured else None,
+                          "min_loudness_in": min(measured) if measured else None,
+                          "max_loudness_in": max(measured) if measured else None}}
+
+    return _corpus_pass("normalize_corpus", ds, out_root, normalizer, batch_size, run, entry, "normalizer",
+                        "loudness.json", totals=totals)

@@ -352,6 +352,56 @@ def _need(what, t, numel, dtype):
         raise _lib.TT2Error(f"{what}: needs {numel} elements of {dtype}, got {t.numel()} of {t.dtype}")
 
 
+# The validators of the data-path wrappers (dtw .. regulate_*).  Each raises `err` with the op and the
+# argument named: TT2Error by default, ValueError for regulate_*.
+
+def _ld(t):
+    """The leading dimension of a [..., rows, cols] view: its row stride, except that a single row's
+    stride is arbitrary, so there any value that covers the row."""
+    return t.stride(-2) if t.shape[-2] > 1 else max(t.stride(-2), t.shape[-1])
+
+
+def _rows(who, name, t, dtype, rows=None, min_cols=0, err=_lib.TT2Error):
+    """Check that t is a 2-D view of `dtype` with a contiguous last dim whose rows do not overlap, of
+    `rows` rows (None: any) and at least min_cols columns; returns its leading dimension."""
+    if t.dtype != dtype or t.dim() != 2 or (t.shape[1] > 1 and t.stride(1) != 1):
+        raise err(f"{who}: {name} must be {dtype} [rows, cols] with a contiguous last dim, "
+                  f"got {t.dtype} {tuple(t.shape)} of strides {t.stride()}")
+    if (rows is not None and t.shape[0] != rows) or t.shape[1] < min_cols:
+        raise err(f"{who}: {name} must be [{'any' if rows is None else rows}, >= {min_cols}], got {tuple(t.shape)}")
+    ld = _ld(t)
+    if ld < t.shape[1]:
+        raise err(f"{who}: {name}'s rows overlap (stride {t.stride(0)} below {t.shape[1]} columns)")
+    return ld
+
+
+def _vec(who, name, t, n, dtype, exact=False, err=_lib.TT2Error):
+    """Check that t (None: skipped) is contiguous, of `dtype`, and holds n elements: at least n in any
+    shape, or with exact=True exactly [n]."""
+    if t is None:
+        return
+    short = (t.dim() != 1 or t.shape[0] != n) if exact else t.numel() < n
+    if t.dtype != dtype or short or not t.is_contiguous():
+        raise err(f"{who}: {name} must be a contiguous {dtype} [{n}], got {t.dtype} {tuple(t.shape)}")
+
+
+def _same_gpu(who, tensors, err=_lib.TT2Error):
+    """Check that every tensor (None: skipped) is on one and the same GPU."""
+    dev = None
+    for t in tensors:
+        if t is not None:
+            dev = t.device if dev is None else dev
+            if not t.is_cuda or t.device != dev:
+                raise err(f"{who}: every tensor must be on the same GPU")
+
+
+def _bind_workspace(g, need, ws):
+    """Point g.workspace at `need` bytes of ws (None: the module's Workspace)."""
+    if need:
+        buf = (ws or _WS).get(need)
+        g.workspace, g.workspace_bytes = buf.data_ptr(), buf.numel()
+
+
 def _span(ld, rows, cols=64):
     """Elements a [rows, >= cols] tensor (or column-slice view of row stride ld) holds at least."""
     if rows > 0 and ld < cols:
@@ -581,33 +631,19 @@ def dtw(a, b, total, length, a_len=None, b_len=None, cols=None, path_a=None, pat
         raise _lib.TT2Error(f"{who}: cols {(c0, c1)} must lie in both tensors and span 1..{_lib.DTW_MAX_FEATS}")
     if (path_a is None) != (path_b is None):
         raise _lib.TT2Error(f"{who}: give both path_a and path_b or neither")
-    _need(f"{who}: total", total, B, torch.float32)
-    _need(f"{who}: length", length, B, torch.int32)
-    tensors = [a, b, total, length]
-    for name, t in (("a_len", a_len), ("b_len", b_len)):
-        if t is not None:
-            _need(f"{who}: {name}", t, B, torch.int32)
-            tensors.append(t)
-    if path_a is not None:
-        for name, t in (("path_a", path_a), ("path_b", path_b)):
-            _need(f"{who}: {name}", t, B * max(0, ta + tb - 1), torch.int32)
-            tensors.append(t)
-    for t in tensors:
-        if t.device != a.device or not t.is_cuda:
-            raise _lib.TT2Error(f"{who}: every tensor must be on a's GPU")
-        if t is not a and t is not b and not t.is_contiguous():
-            raise _lib.TT2Error(f"{who}: outputs and lengths must be contiguous")
+    _vec(who, "total", total, B, torch.float32)
+    for name, t in (("length", length), ("a_len", a_len), ("b_len", b_len)):
+        _vec(who, name, t, B, torch.int32)
+    for name, t in (("path_a", path_a), ("path_b", path_b)):
+        _vec(who, name, t, B * max(0, ta + tb - 1), torch.int32)
+    _same_gpu(who, (a, b, total, length, a_len, b_len, path_a, path_b))
     g = _lib.DtwArgs()
     g.a, g.b, g.a_len, g.b_len = a.data_ptr(), b.data_ptr(), ptr(a_len), ptr(b_len)
     g.total, g.length, g.path_a, g.path_b = total.data_ptr(), length.data_ptr(), ptr(path_a), ptr(path_b)
-    g.a_ld, g.b_ld = (a.stride(1) if ta > 1 else max(a.stride(1), a.shape[2])), \
-        (b.stride(1) if tb > 1 else max(b.stride(1), b.shape[2]))
+    g.a_ld, g.b_ld = _ld(a), _ld(b)
     g.batch, g.ta, g.tb, g.c0, g.c1 = B, ta, tb, c0, c1
     L = lib()
-    need = L.tt2_dtw_workspace_size(B, ta, tb, int(path_a is not None))
-    if need:
-        buf = (ws or _WS).get(need)
-        g.workspace, g.workspace_bytes = buf.data_ptr(), buf.numel()
+    _bind_workspace(g, L.tt2_dtw_workspace_size(B, ta, tb, int(path_a is not None)), ws)
     check(L.tt2_dtw(C.byref(g), stream_ptr()), "tt2_dtw")
     return total, length
 
@@ -628,26 +664,17 @@ def yin(x, utt_stride, f0, lag, aper, energy, hop, tau_min, tau_max, sr, thresho
     utt_stride, hop = int(utt_stride), int(hop)
     if B and T and (utt_stride < 0 or hop < 1 or (B - 1) * utt_stride + (T - 1) * hop + _lib.YIN_FRAME > x.numel()):
         raise _lib.TT2Error(f"{who}: x holds {x.numel()} samples, fewer than the last frame needs")
-    tensors = [x]
     for name, t, dtype in (("f0", f0, torch.float32), ("lag", lag, torch.int32), ("aper", aper, torch.float32),
                            ("energy", energy, torch.float32)):
-        _need(f"{who}: {name}", t, B * T, dtype)
-        tensors.append(t)
-    if frames is not None:
-        _need(f"{who}: frames", frames, B, torch.int32)
-        tensors.append(frames)
+        _vec(who, name, t, B * T, dtype)
+    _vec(who, "frames", frames, B, torch.int32)
     ld = 0
     if cmnd is not None:
         if cmnd.dim() != 3 or cmnd.shape[0] != B or cmnd.shape[1] != T:
             raise _lib.TT2Error(f"{who}: cmnd must be [B, T, ld]")
         ld = cmnd.shape[2]
-        _need(f"{who}: cmnd", cmnd, B * T * ld, torch.float32)
-        tensors.append(cmnd)
-    for t in tensors:
-        if t.device != f0.device or not t.is_cuda:
-            raise _lib.TT2Error(f"{who}: every tensor must be on f0's GPU")
-        if not t.is_contiguous():
-            raise _lib.TT2Error(f"{who}: every tensor must be contiguous")
+        _vec(who, "cmnd", cmnd, B * T * ld, torch.float32)
+    _same_gpu(who, (f0, x, lag, aper, energy, frames, cmnd))
     g = _lib.YinArgs()
     g.x, g.frames, g.cmnd = x.data_ptr(), ptr(frames), ptr(cmnd)
     g.f0, g.lag, g.aper, g.energy = f0.data_ptr(), lag.data_ptr(), aper.data_ptr(), energy.data_ptr()
@@ -676,22 +703,15 @@ def pitch_track(cmnd, frames, f0, lag, cost, tau_min, tau_max, sr, pos, jump, sw
         raise _lib.TT2Error(f"{who}: {T} frames exceed {_lib.PITCH_TRACK_MAX_FRAMES}")
     if width < tau_max + 1:
         raise _lib.TT2Error(f"{who}: cmnd rows hold {width} values, fewer than tau_max + 1")
-    ld = cmnd.stride(1) if T > 1 else max(cmnd.stride(1), width)
+    ld = _ld(cmnd)
     if ld < width or (B > 1 and T > 0 and cmnd.stride(0) != T * ld):
         raise _lib.TT2Error(f"{who}: cmnd's rows must follow one another (stride(0) = T * stride(1) >= ld)")
-    _need(f"{who}: f0", f0, B * T, torch.float32)
-    _need(f"{who}: lag", lag, B * T, torch.int32)
-    _need(f"{who}: cost", cost, B, torch.float32)
-    _need(f"{who}: pos", pos, tau_max + 1, torch.float32)
-    tensors = [cmnd, f0, lag, cost, pos]
-    if frames is not None:
-        _need(f"{who}: frames", frames, B, torch.int32)
-        tensors.append(frames)
-    for t in tensors:
-        if t.device != cmnd.device or not t.is_cuda:
-            raise _lib.TT2Error(f"{who}: every tensor must be on cmnd's GPU")
-        if t is not cmnd and not t.is_contiguous():
-            raise _lib.TT2Error(f"{who}: outputs, frames and pos must be contiguous")
+    _vec(who, "f0", f0, B * T, torch.float32)
+    _vec(who, "lag", lag, B * T, torch.int32)
+    _vec(who, "cost", cost, B, torch.float32)
+    _vec(who, "pos", pos, tau_max + 1, torch.float32)
+    _vec(who, "frames", frames, B, torch.int32)
+    _same_gpu(who, (cmnd, f0, lag, cost, pos, frames))
     g = _lib.PitchTrackArgs()
     g.cmnd, g.frames, g.pos = cmnd.data_ptr(), ptr(frames), pos.data_ptr()
     g.f0, g.lag, g.cost = f0.data_ptr(), lag.data_ptr(), cost.data_ptr()
@@ -699,10 +719,7 @@ def pitch_track(cmnd, frames, f0, lag, cost, tau_min, tau_max, sr, pos, jump, sw
     g.batch, g.t, g.tau_min, g.tau_max = B, T, tau_min, tau_max
     g.sr, g.jump, g.switch_cost, g.unvoiced = float(sr), float(jump), float(switch), float(unvoiced)
     L = lib()
-    need = L.tt2_pitch_track_workspace_size(B, T, tau_min, tau_max)
-    if need:
-        buf = (ws or _WS).get(need)
-        g.workspace, g.workspace_bytes = buf.data_ptr(), buf.numel()
+    _bind_workspace(g, L.tt2_pitch_track_workspace_size(B, T, tau_min, tau_max), ws)
     check(L.tt2_pitch_track(C.byref(g), stream_ptr()), "tt2_pitch_track")
     return f0, lag, cost
 
@@ -721,35 +738,17 @@ def resample(x, y, bank, up, down, half, lens=None, out_lens=None):
     K = 2 * half + 1
     if half < 0 or K > _lib.RESAMPLE_MAX_TAPS:
         raise _lib.TT2Error(f"{who}: 2 * half + 1 = {K} taps outside 1 .. {_lib.RESAMPLE_MAX_TAPS}")
-    for name, t in (("x", x), ("y", y), ("bank", bank)):
-        if t.dtype != torch.float32 or t.dim() != 2 or (t.shape[1] > 1 and t.stride(1) != 1):
-            raise _lib.TT2Error(f"{who}: {name} must be f32 [rows, cols] with a contiguous last dim")
-    if x.shape[0] != y.shape[0]:
-        raise _lib.TT2Error(f"{who}: x has {x.shape[0]} rows, y {y.shape[0]}")
-    B, n_in = x.shape
-    n_out = y.shape[1]
-    if bank.shape[0] != up or bank.shape[1] < K:
-        raise _lib.TT2Error(f"{who}: bank must be [{up}, >= {K}], got {list(bank.shape)}")
-
-    def ld(t):   # a single row's stride is arbitrary: any value that covers the row
-        return t.stride(0) if t.shape[0] > 1 else max(t.stride(0), t.shape[1])
-
-    for name, t in (("x", x), ("y", y), ("bank", bank)):
-        if ld(t) < t.shape[1]:
-            raise _lib.TT2Error(f"{who}: {name}'s rows overlap (stride {t.stride(0)} below {t.shape[1]} columns)")
-    tensors = [x, y, bank]
-    for name, t in (("lens", lens), ("out_lens", out_lens)):
-        if t is not None:
-            _need(f"{who}: {name}", t, B, torch.int32)
-            if not t.is_contiguous():
-                raise _lib.TT2Error(f"{who}: {name} must be contiguous")
-            tensors.append(t)
-    for t in tensors:
-        if t.device != y.device or not t.is_cuda:
-            raise _lib.TT2Error(f"{who}: every tensor must be on y's GPU")
+    y_ld = _rows(who, "y", y, torch.float32)
+    B, n_out = y.shape
+    x_ld = _rows(who, "x", x, torch.float32, rows=B)
+    n_in = x.shape[1]
+    bank_ld = _rows(who, "bank", bank, torch.float32, rows=up, min_cols=K)
+    _vec(who, "lens", lens, B, torch.int32)
+    _vec(who, "out_lens", out_lens, B, torch.int32)
+    _same_gpu(who, (y, x, bank, lens, out_lens))
     g = _lib.ResampleArgs()
     g.x, g.lens, g.bank, g.y, g.out_lens = x.data_ptr(), ptr(lens), bank.data_ptr(), y.data_ptr(), ptr(out_lens)
-    g.x_ld, g.y_ld, g.bank_ld = ld(x), ld(y), ld(bank)
+    g.x_ld, g.y_ld, g.bank_ld = x_ld, y_ld, bank_ld
     g.batch, g.n_in, g.n_out, g.up, g.down, g.half = B, n_in, n_out, up, down, half
     check(lib().tt2_resample(C.byref(g), stream_ptr()), "tt2_resample")
     return y, out_lens
@@ -771,43 +770,21 @@ def trim(x, y, hop, r, keep, ratio, lens=None, out_lens=None, start=None, energy
         raise _lib.TT2Error(f"{who}: hop >= 1, 1 <= r <= {_lib.TRIM_MAX_R} and 2 * r * hop within int32, got {hop}, {r}")
     if keep < 0 or not (0.0 <= ratio <= 1.0):
         raise _lib.TT2Error(f"{who}: keep >= 0 and 0 <= ratio <= 1, got {keep}, {ratio}")
-    views = [("x", x), ("y", y)] + ([("energy", energy)] if energy is not None else [])
-    for name, t in views:
-        if t.dtype != torch.float32 or t.dim() != 2 or (t.shape[1] > 1 and t.stride(1) != 1):
-            raise _lib.TT2Error(f"{who}: {name} must be f32 [rows, cols] with a contiguous last dim")
-        if t.shape[0] != y.shape[0]:
-            raise _lib.TT2Error(f"{who}: {name} has {t.shape[0]} rows, y {y.shape[0]}")
-    B, n_in = x.shape
-    n_out = y.shape[1]
-    if energy is not None and energy.shape[1] < n_in // hop + 1:
-        raise _lib.TT2Error(f"{who}: energy needs {n_in // hop + 1} columns, got {energy.shape[1]}")
-
-    def ld(t):   # a single row's stride is arbitrary: any value that covers the row
-        return t.stride(0) if t.shape[0] > 1 else max(t.stride(0), t.shape[1])
-
-    for name, t in views:
-        if ld(t) < t.shape[1]:
-            raise _lib.TT2Error(f"{who}: {name}'s rows overlap (stride {t.stride(0)} below {t.shape[1]} columns)")
-    tensors = [t for _, t in views]
+    y_ld = _rows(who, "y", y, torch.float32)
+    B, n_out = y.shape
+    x_ld = _rows(who, "x", x, torch.float32, rows=B)
+    n_in = x.shape[1]
+    energy_ld = 0 if energy is None else _rows(who, "energy", energy, torch.float32, rows=B, min_cols=n_in // hop + 1)
     for name, t in (("lens", lens), ("out_lens", out_lens), ("start", start)):
-        if t is not None:
-            _need(f"{who}: {name}", t, B, torch.int32)
-            if not t.is_contiguous():
-                raise _lib.TT2Error(f"{who}: {name} must be contiguous")
-            tensors.append(t)
-    for t in tensors:
-        if t.device != y.device or not t.is_cuda:
-            raise _lib.TT2Error(f"{who}: every tensor must be on y's GPU")
+        _vec(who, name, t, B, torch.int32)
+    _same_gpu(who, (y, x, energy, lens, out_lens, start))
     g = _lib.TrimArgs()
     g.x, g.lens, g.y = x.data_ptr(), ptr(lens), y.data_ptr()
     g.out_lens, g.start, g.energy = ptr(out_lens), ptr(start), ptr(energy)
-    g.x_ld, g.y_ld, g.energy_ld = ld(x), ld(y), (ld(energy) if energy is not None else 0)
+    g.x_ld, g.y_ld, g.energy_ld = x_ld, y_ld, energy_ld
     g.batch, g.n_in, g.n_out, g.hop, g.r, g.keep, g.ratio = B, n_in, n_out, hop, r, keep, ratio
     L = lib()
-    need = L.tt2_trim_workspace_size(B, n_in, hop)
-    if need:
-        buf = (workspace or _WS).get(need)
-        g.workspace, g.workspace_bytes = buf.data_ptr(), buf.numel()
+    _bind_workspace(g, L.tt2_trim_workspace_size(B, n_in, hop), workspace)
     check(L.tt2_trim(C.byref(g), stream_ptr()), "tt2_trim")
     return y, out_lens, start, energy
 
@@ -836,74 +813,30 @@ def loudness(x, step, coef, abs_sum, rel_ratio, target_ms, ceiling, lens=None, y
         raise _lib.TT2Error(f"{who}: abs_sum finite and >= 0 and 0 <= rel_ratio <= 1, got {abs_sum}, {rel_ratio}")
     if not (math.isfinite(target_ms) and target_ms > 0.0 and math.isfinite(ceiling) and ceiling > 0.0):
         raise _lib.TT2Error(f"{who}: target_ms and ceiling finite and > 0, got {target_ms}, {ceiling}")
-    vecs = [(n, t) for n, t in (("loud", loud), ("gain", gain), ("peak", peak), ("limited", limited)) if t is not None]
-    views = [(n, t) for n, t in (("x", x), ("y", y), ("energy", energy)) if t is not None]
-    if len(views) == 1 and not vecs:
+    outputs = (y, loud, gain, peak, limited, energy)
+    if all(t is None for t in outputs):
         raise _lib.TT2Error(f"{who}: at least one output is required")
-    for name, t in views:
-        if t.dtype != torch.float32 or t.dim() != 2 or (t.shape[1] > 1 and t.stride(1) != 1):
-            raise _lib.TT2Error(f"{who}: {name} must be f32 [rows, cols] with a contiguous last dim")
-        if t.shape[0] != x.shape[0]:
-            raise _lib.TT2Error(f"{who}: {name} has {t.shape[0]} rows, x {x.shape[0]}")
+    x_ld = _rows(who, "x", x, torch.float32)
     B, n_in = x.shape
+    y_ld = 0 if y is None else _rows(who, "y", y, torch.float32, rows=B)
     n_out = y.shape[1] if y is not None else 0
-    if energy is not None and energy.shape[1] < n_in // step + 1:
-        raise _lib.TT2Error(f"{who}: energy needs {n_in // step + 1} columns, got {energy.shape[1]}")
-
-    def ld(t):   # a single row's stride is arbitrary: any value that covers the row
-        return t.stride(0) if t.shape[0] > 1 else max(t.stride(0), t.shape[1])
-
-    for name, t in views:
-        if ld(t) < t.shape[1]:
-            raise _lib.TT2Error(f"{who}: {name}'s rows overlap (stride {t.stride(0)} below {t.shape[1]} columns)")
-    tensors = [t for _, t in views]
-    for name, t in vecs + ([("lens", lens)] if lens is not None else []):
-        _need(f"{who}: {name}", t, B, torch.int32 if name in ("lens", "limited") else torch.float32)
-        if not t.is_contiguous():
-            raise _lib.TT2Error(f"{who}: {name} must be contiguous")
-        tensors.append(t)
-    for t in tensors:
-        if t.device != x.device or not t.is_cuda:
-            raise _lib.TT2Error(f"{who}: every tensor must be on x's GPU")
+    energy_ld = 0 if energy is None else _rows(who, "energy", energy, torch.float32, rows=B, min_cols=n_in // step + 1)
+    for name, t in (("loud", loud), ("gain", gain), ("peak", peak)):
+        _vec(who, name, t, B, torch.float32)
+    _vec(who, "limited", limited, B, torch.int32)
+    _vec(who, "lens", lens, B, torch.int32)
+    _same_gpu(who, (x, lens) + outputs)
     g = _lib.LoudnessArgs()
     g.x, g.lens, g.y = x.data_ptr(), ptr(lens), ptr(y)
     g.loud, g.gain, g.peak, g.limited, g.energy = ptr(loud), ptr(gain), ptr(peak), ptr(limited), ptr(energy)
-    g.x_ld, g.y_ld = ld(x), (ld(y) if y is not None else 0)
-    g.energy_ld = ld(energy) if energy is not None else 0
+    g.x_ld, g.y_ld, g.energy_ld = x_ld, y_ld, energy_ld
     g.batch, g.n_in, g.n_out, g.step = B, n_in, n_out, step
     g.coef = (C.c_double * 10)(*coef)
     g.abs_sum, g.rel_ratio, g.target_ms, g.ceiling = abs_sum, rel_ratio, target_ms, ceiling
     L = lib()
-    need = L.tt2_loudness_workspace_size(B, n_in, step)
-    if need:
-        buf = (workspace or _WS).get(need)
-        g.workspace, g.workspace_bytes = buf.data_ptr(), buf.numel()
+    _bind_workspace(g, L.tt2_loudness_workspace_size(B, n_in, step), workspace)
     check(L.tt2_loudness(C.byref(g), stream_ptr()), "tt2_loudness")
     return y, loud, gain, peak, limited, energy
-
-
-def _rg_rows(who, name, t, rows, cols, dtype=torch.int32):
-    """A [rows, >= cols] view of `dtype` with a contiguous last dim; returns its leading dimension."""
-    if t.dtype != dtype or t.dim() != 2 or t.shape[0] != rows or t.shape[1] < cols:
-        raise ValueError(f"{who}: {name} must be {dtype} [{rows}, >= {cols}], got {t.dtype} {tuple(t.shape)}")
-    if t.shape[1] > 1 and t.stride(1) != 1:
-        raise ValueError(f"{who}: {name} needs a contiguous last dim")
-    ld = t.stride(0) if rows > 1 else max(t.stride(0), t.shape[1])   # a single row's stride is arbitrary
-    if ld < t.shape[1]:
-        raise ValueError(f"{who}: {name}'s rows overlap (stride {t.stride(0)} below {t.shape[1]} columns)")
-    return ld
-
-
-def _rg_vec(who, name, t, rows):
-    if t is not None and (t.dtype != torch.int32 or t.dim() != 1 or t.shape[0] != rows or not t.is_contiguous()):
-        raise ValueError(f"{who}: {name} must be a contiguous int32 [{rows}], got {t.dtype} {tuple(t.shape)}")
-
-
-def _rg_same_gpu(who, tensors):
-    dev = tensors[0].device
-    for t in tensors:
-        if t is not None and (not t.is_cuda or t.device != dev):
-            raise ValueError(f"{who}: every tensor must be on the same GPU")
 
 
 def regulate_plan(durations, n_out, key_len=None, ends=None, index=None, frames=None, total=None):
@@ -916,8 +849,7 @@ def regulate_plan(durations, n_out, key_len=None, ends=None, index=None, frames=
     synchronisation.  Deterministic."""
     who = "regulate_plan"
     n_out = int(n_out)
-    if durations.dim() != 2 or durations.dtype != torch.int32:
-        raise ValueError(f"{who}: durations must be int32 [B, Tx], got {durations.dtype} {tuple(durations.shape)}")
+    dur_ld = _rows(who, "durations", durations, torch.int32, err=ValueError)
     B, tx = durations.shape
     if tx > _lib.REGULATE_MAX_PHONEMES:
         raise ValueError(f"{who}: Tx = {tx} above TT2_REGULATE_MAX_PHONEMES = {_lib.REGULATE_MAX_PHONEMES}")
@@ -926,13 +858,13 @@ def regulate_plan(durations, n_out, key_len=None, ends=None, index=None, frames=
     if ends is None:
         raise ValueError(f"{who}: ends is required")
     g = _lib.RegulatePlanArgs()
-    g.dur_ld = _rg_rows(who, "durations", durations, B, tx)
-    g.ends_ld = _rg_rows(who, "ends", ends, B, tx)
+    g.dur_ld = dur_ld
+    g.ends_ld = _rows(who, "ends", ends, torch.int32, rows=B, min_cols=tx, err=ValueError)
     if index is not None:
-        g.index_ld = _rg_rows(who, "index", index, B, n_out)
+        g.index_ld = _rows(who, "index", index, torch.int32, rows=B, min_cols=n_out, err=ValueError)
     for name, t in (("key_len", key_len), ("frames", frames), ("total", total)):
-        _rg_vec(who, name, t, B)
-    _rg_same_gpu(who, [durations, ends, index, key_len, frames, total])
+        _vec(who, name, t, B, torch.int32, exact=True, err=ValueError)
+    _same_gpu(who, (durations, ends, index, key_len, frames, total), err=ValueError)
     g.durations, g.key_len, g.ends, g.index = durations.data_ptr(), ptr(key_len), ends.data_ptr(), ptr(index)
     g.frames, g.total = ptr(frames), ptr(total)
     g.batch, g.tx, g.n_out = B, tx, n_out
@@ -954,14 +886,14 @@ def _regulate_args(who, src, dst, map_, map_cols):
     for name, t in (("src", src), ("dst", dst)):
         if D > 1 and t.stride(2) != 1:
             raise ValueError(f"{who}: {name} needs a contiguous last dim")
-        ld = t.stride(1) if t.shape[1] > 1 else max(t.stride(1), D)
+        ld = _ld(t)
         bs = t.stride(0) if B > 1 else max(t.stride(0), 0)
         if ld < D or (name == "dst" and B > 1 and t.shape[1] > 0 and bs < (t.shape[1] - 1) * ld + D):
             raise ValueError(f"{who}: {name}'s rows overlap (strides {t.stride()} for {tuple(t.shape)})")
         strides += [ld, bs]
     g.src_ld, g.src_bs, g.dst_ld, g.dst_bs = strides
-    g.map_ld = _rg_rows(who, "map", map_, B, map_cols)
-    _rg_same_gpu(who, [dst, src, map_])
+    g.map_ld = _rows(who, "map", map_, torch.int32, rows=B, min_cols=map_cols, err=ValueError)
+    _same_gpu(who, (dst, src, map_), err=ValueError)
     g.src, g.dst, g.map = src.data_ptr(), dst.data_ptr(), map_.data_ptr()
     g.batch, g.dim, g.dtype = B, D, dt(dst)
     return g
