@@ -740,6 +740,88 @@ int tt2_regulate_plan(const tt2_regulate_plan_args* a, hipStream_t stream);
 int tt2_regulate_fwd(const tt2_regulate_args* a, hipStream_t stream);
 int tt2_regulate_bwd(const tt2_regulate_args* a, hipStream_t stream);
 
+/* ---------------------------------------------------------- forward-sum alignment loss
+ * The total probability of all monotone alignments of a (frame, phoneme) score matrix, its
+ * posterior, its gradient and its best path: the teacher-free alignment learning of RAD-TTS /
+ * FastPitch 1.1 / JETS (CTC over the phoneme sequence without a useful blank; Badlani et al. 2021).
+ * One work group per utterance, no host synchronisation, no floating-point atomics and every order
+ * fixed: all outputs are bit-identical run to run.
+ *   Inputs.  For utterance b, Ty = clamp(q_len[b], 0, tq), Tx = clamp(key_len[b], 0, tk) and
+ * Te = min(Tx, Ty); a NULL length vector means tq / tk.  Score s[n][t] (f32) is at
+ * scores + b * s_bs + n * s_ld + t, the strides in elements, so [B, 1, Ty, Tx] tensors and column
+ * slices go in as they are.  ls[n][t] = s[n][t] - ln sum_{u < Tx} exp s[n][u]: the log-softmax runs
+ * over the utterance's own phonemes only and is fused; a caller with a prior passes
+ * scores + log_prior.  Rows n >= Ty and columns t >= Tx are never read.
+ *   Paths.  tt2_align_monotonic's set: pi(0) = 0, pi(Ty-1) = Te-1, pi(n+1) - pi(n) in {0, 1}.
+ *   Partition and loss.  Z = sum_pi prod_n exp ls[n][pi(n)], loss[b] = -ln Z in nats; 0 when Ty = 0
+ * or Tx = 0.
+ *   Posterior.  gamma[n][t] = P(pi(n) = t) = exp(alpha[n][t] + beta[n][t] - ln Z) with
+ *     alpha[0][0] = ls[0][0], alpha[n][t] = ls[n][t] + logaddexp(alpha[n-1][t], alpha[n-1][t-1]),
+ *     beta[Ty-1][Te-1] = 0,
+ *     beta[n][t] = logaddexp(ls[n+1][t] + beta[n+1][t], ls[n+1][t+1] + beta[n+1][t+1]).
+ * Every row of gamma sums to 1.
+ *   Gradient.  dscores[n][t] = grad_loss[b] * (P[n][t] - gamma[n][t]) with P = exp ls: every path
+ * visits every row once, so this is the exact gradient with respect to the raw scores.  grad_loss is
+ * a device vector [batch]; NULL means 1.
+ *   Padding.  gamma and dscores are exactly +0 for n >= Ty or t >= Tx; they are written for every
+ * n < tq, t < tk and nothing at or past column tk.
+ *   Numerics.  ls is formed as (s - m) - ln sum exp(s - m) with m the row's maximum, which keeps the
+ * precision of a small ls; lse = m + that logarithm.  alpha and beta are carried relative to a per-row offset, the row's maximum, which is
+ * subtracted after every row; the offsets are summed in float64, so the stored values stay O(ln Tx)
+ * near the mass.  A cell no path reaches holds -1e30 instead of -inf.  gamma[n][.] is the softmax
+ * over t of the stored alpha + beta, in which the offsets cancel.
+ *   tt2_forward_sum_fwd writes loss [batch], the row log-sum-exps lse [batch, tq] (0 for n >= Ty)
+ * and, unless alpha is NULL, the renormalised alpha [batch, tq, a_ld] for n < Ty, t < Te (its other
+ * cells are left as they were; only tt2_forward_sum_bwd reads it).  A loss-only call (alpha NULL)
+ * gives the same loss bit for bit.  No workspace.
+ *   tt2_forward_sum_bwd reads scores, lse and alpha as tt2_forward_sum_fwd left them, runs the beta
+ * pass into `workspace` (16-B aligned, tt2_forward_sum_bwd_workspace_size bytes) and writes dscores
+ * and / or gamma (either may be NULL, not both) in a second, element-parallel launch.
+ *   tt2_forward_sum_path is the binarisation: V, move (strict: a tie stays) and the backtrack are
+ * tt2_align_monotonic's, over the raw f32 s with one add per cell and no renormalisation.
+ *     path[b][n]      = pi(n) for n < Ty, -1 for n >= Ty
+ *     durations[b][t] = #{n : pi(n) = t}, 0 for t >= Te
+ *     logp[b]         = (sum over n < Ty of ls[n][pi(n)]) / Ty, the sum in a fixed order
+ * Ty = 0 or Tx = 0 gives -1, 0 and 0.  The move bits stay in LDS when they fit, as in
+ * tt2_align_monotonic; otherwise they go to `workspace` (8-B aligned,
+ * tt2_forward_sum_path_workspace_size bytes, 0 when LDS suffices).
+ *   Contract.  Scores are finite.  NaN or +-inf inside one utterance may make that utterance's
+ * outputs NaN; every other utterance's outputs stay bit-identical.
+ *   Limits: tk <= TT2_FSUM_MAX_KEYS, tq <= TT2_FSUM_MAX_FRAMES, f32 scores and gradients only.
+ *   Refused with TT2_E_INVALID before any launch, with a message that starts with the entry's name:
+ * null args; batch, tq or tk negative; tq or tk over the limits; s_ld < tk; alpha given (fwd) or
+ * needed (bwd) with a_ld < tk; dscores given with d_ld < tk, gamma given with g_ld < tk; more than
+ * 2^31 - 1 work groups; a workspace that is too small or misaligned; then, where the call has
+ * something to do, a null pointer it would read or write: loss (fwd, batch > 0), lse (fwd with
+ * tq > 0; bwd), scores (batch, tq and tk positive), alpha (bwd), both of dscores and gamma (bwd),
+ * path with tq > 0, durations with tk > 0 and logp (path).
+ *   Zero sizes.  batch = 0 succeeds without a launch, in all three.  With tq = 0 or tk = 0, fwd writes
+ * loss = 0 (and lse = 0), bwd has nothing to write and succeeds without a launch, and path writes
+ * path = -1, durations = 0 and logp = 0 where they exist. */
+#define TT2_FSUM_MAX_KEYS 512
+#define TT2_FSUM_MAX_FRAMES 4096
+typedef struct tt2_forward_sum_args {
+  const float* scores;       /* s[b][n][t] at scores + b * s_bs + n * s_ld + t */
+  const int32_t* q_len; const int32_t* key_len;   /* [batch], device (NULL: tq / tk) */
+  float* loss;               /* [batch]: fwd writes */
+  float* lse;                /* [batch, tq]: fwd writes, bwd reads */
+  float* alpha;              /* [batch, tq, a_ld]: fwd writes (optional), bwd reads */
+  const float* grad_loss;    /* [batch], device (NULL: 1): bwd reads */
+  float* dscores;            /* d[b][n][t] at dscores + b * d_bs + n * d_ld + t: bwd writes (optional) */
+  float* gamma;              /* the same with g_bs, g_ld: bwd writes (optional) */
+  int32_t* path;             /* [batch, tq]: path writes */
+  int32_t* durations;        /* [batch, tk]: path writes */
+  float* logp;               /* [batch]: path writes */
+  void* workspace; size_t workspace_bytes;
+  int64_t s_ld, s_bs, a_ld, d_ld, d_bs, g_ld, g_bs;   /* in elements */
+  int32_t batch, tq, tk;
+} tt2_forward_sum_args;
+size_t tt2_forward_sum_bwd_workspace_size(int batch, int tq, int tk);
+size_t tt2_forward_sum_path_workspace_size(int batch, int tq, int tk);
+int tt2_forward_sum_fwd(const tt2_forward_sum_args* a, hipStream_t stream);
+int tt2_forward_sum_bwd(const tt2_forward_sum_args* a, hipStream_t stream);
+int tt2_forward_sum_path(const tt2_forward_sum_args* a, hipStream_t stream);
+
 /* ------------------------------------------------------------------ decode
  * One query row per batch element (the AR decode step):
  * out[b*o_ld + 64h ..] = softmax(scale q k^T) v over keys j < n_b of batch b,

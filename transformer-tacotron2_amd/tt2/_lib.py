@@ -372,6 +372,30 @@ SIGNATURES.update({
 })
 
 
+FSUM_MAX_KEYS = 512      # TT2_FSUM_MAX_KEYS
+FSUM_MAX_FRAMES = 4096   # TT2_FSUM_MAX_FRAMES
+
+
+class ForwardSumArgs(C.Structure):
+    """tt2_forward_sum_args: the forward-sum alignment loss, its gradient / posterior and its best path."""
+    _fields_ = [
+        ("scores", vp), ("q_len", vp), ("key_len", vp), ("loss", vp), ("lse", vp), ("alpha", vp),
+        ("grad_loss", vp), ("dscores", vp), ("gamma", vp), ("path", vp), ("durations", vp), ("logp", vp),
+        ("workspace", vp), ("workspace_bytes", sz),
+        ("s_ld", i64), ("s_bs", i64), ("a_ld", i64), ("d_ld", i64), ("d_bs", i64), ("g_ld", i64), ("g_bs", i64),
+        ("batch", i32), ("tq", i32), ("tk", i32),
+    ]
+
+
+SIGNATURES.update({
+    "tt2_forward_sum_bwd_workspace_size": ([C.c_int, C.c_int, C.c_int], C.c_size_t),
+    "tt2_forward_sum_path_workspace_size": ([C.c_int, C.c_int, C.c_int], C.c_size_t),
+    "tt2_forward_sum_fwd": ([C.POINTER(ForwardSumArgs), vp], C.c_int),
+    "tt2_forward_sum_bwd": ([C.POINTER(ForwardSumArgs), vp], C.c_int),
+    "tt2_forward_sum_path": ([C.POINTER(ForwardSumArgs), vp], C.c_int),
+})
+
+
 class ReduceArgs(C.Structure):
     _fields_ = [("src", vp), ("dst", vp), ("ld", i64), ("rows", i32), ("cols", i32), ("beta", f32)]
 

@@ -353,7 +353,7 @@ def _need(what, t, numel, dtype):
 
 
 # The validators of the data-path wrappers (dtw .. regulate_*).  Each raises `err` with the op and the
-# argument named: TT2Error by default, ValueError for regulate_*.
+# argument named: TT2Error by default, ValueError for regulate_* and forward_sum_*.
 
 def _ld(t):
     """The leading dimension of a [..., rows, cols] view: its row stride, except that a single row's
@@ -928,6 +928,119 @@ def regulate_bwd(dy, ends, dh):
     g.tx, g.n_out = dh.shape[1], dy.shape[1]
     check(lib().tt2_regulate_bwd(C.byref(g), stream_ptr()), "tt2_regulate_bwd")
     return dh
+
+
+def _fsum_mat(who, name, t, B, tq, tk, out=False):
+    """Check that t is f32 [B, tq, tk] with a contiguous last dim (any row and batch stride; an output's
+    rows and utterances must not overlap); returns (ld, bs) in elements."""
+    if t.dtype != torch.float32 or t.dim() != 3 or (t.shape[2] > 1 and t.stride(2) != 1):
+        raise ValueError(f"{who}: {name} must be f32 [B, Ty, Tx] with a contiguous last dim, "
+                         f"got {t.dtype} {tuple(t.shape)} of strides {t.stride()}")
+    if B is not None and tuple(t.shape) != (B, tq, tk):
+        raise ValueError(f"{who}: {name} is {tuple(t.shape)}, the scores are [{B}, {tq}, {tk}]")
+    ld = _ld(t)
+    bs = t.stride(0) if t.shape[0] > 1 else max(t.stride(0), 0)
+    if ld < t.shape[2] or (out and t.shape[0] > 1 and t.shape[1] > 0 and bs < (t.shape[1] - 1) * ld + t.shape[2]):
+        raise ValueError(f"{who}: {name}'s rows overlap (strides {t.stride()} for {tuple(t.shape)})")
+    return ld, bs
+
+
+def _fsum_args(who, scores, q_len, key_len):
+    g = _lib.ForwardSumArgs()
+    g.s_ld, g.s_bs = _fsum_mat(who, "scores", scores, None, 0, 0)
+    B, tq, tk = scores.shape
+    if tk > _lib.FSUM_MAX_KEYS or tq > _lib.FSUM_MAX_FRAMES:
+        raise ValueError(f"{who}: [Ty, Tx] = [{tq}, {tk}] above TT2_FSUM_MAX_FRAMES = {_lib.FSUM_MAX_FRAMES} / "
+                         f"TT2_FSUM_MAX_KEYS = {_lib.FSUM_MAX_KEYS}")
+    for name, t in (("q_len", q_len), ("key_len", key_len)):
+        _vec(who, name, t, B, torch.int32, exact=True, err=ValueError)
+    g.scores, g.q_len, g.key_len = scores.data_ptr(), ptr(q_len), ptr(key_len)
+    g.batch, g.tq, g.tk = B, tq, tk
+    return g
+
+
+def _fsum_alpha(who, g, alpha):
+    B, tq, tk = g.batch, g.tq, g.tk
+    if alpha.dtype != torch.float32 or alpha.dim() != 3 or alpha.shape[:2] != (B, tq) or alpha.shape[2] < tk or \
+            not alpha.is_contiguous():
+        raise ValueError(f"{who}: alpha must be a contiguous f32 [{B}, {tq}, >= {tk}], got {alpha.dtype} {tuple(alpha.shape)}")
+    g.alpha, g.a_ld = alpha.data_ptr(), max(alpha.shape[2], tk)
+
+
+def forward_sum_fwd(scores, loss, lse, alpha=None, q_len=None, key_len=None):
+    """The forward-sum alignment loss (tt2_forward_sum_fwd; include/tt2_capi.h has the definition):
+    scores [B, Ty, Tx] f32 (any row and batch stride, a contiguous last dim) -> loss [B] f32 = -ln Z
+    in nats, lse [B, Ty] f32 (the row log-sum-exps) and, when given, alpha [B, Ty, >= Tx] f32, the
+    renormalised forward variable that forward_sum_bwd reads.  q_len / key_len [B] int32 bound the
+    frames / phonemes of each utterance (None: Ty / Tx).  On the current stream, no host
+    synchronisation.  Deterministic."""
+    who = "forward_sum_fwd"
+    g = _fsum_args(who, scores, q_len, key_len)
+    _vec(who, "loss", loss, g.batch, torch.float32, exact=True, err=ValueError)
+    if lse is None or loss is None:
+        raise ValueError(f"{who}: loss and lse are required")
+    if lse.dtype != torch.float32 or tuple(lse.shape) != (g.batch, g.tq) or not lse.is_contiguous():
+        raise ValueError(f"{who}: lse must be a contiguous f32 [{g.batch}, {g.tq}], got {lse.dtype} {tuple(lse.shape)}")
+    if alpha is not None:
+        _fsum_alpha(who, g, alpha)
+    _same_gpu(who, (scores, loss, lse, alpha, q_len, key_len), err=ValueError)
+    g.loss, g.lse = loss.data_ptr(), lse.data_ptr()
+    check(lib().tt2_forward_sum_fwd(C.byref(g), stream_ptr()), "tt2_forward_sum_fwd")
+    return loss, lse, alpha
+
+
+def forward_sum_bwd(scores, lse, alpha, dscores=None, gamma=None, grad_loss=None, q_len=None, key_len=None,
+                    workspace=None):
+    """The gradient and posterior of the forward-sum loss (tt2_forward_sum_bwd): with scores, lse and
+    alpha as forward_sum_fwd left them, dscores [B, Ty, Tx] f32 = grad_loss[b] * (softmax(scores) -
+    gamma) and gamma [B, Ty, Tx] f32 = P(pi(n) = t), both exactly 0 in the padding; either may be
+    None, not both, and both may be slices of wider buffers.  grad_loss [B] f32 on the device (None:
+    1).  workspace: a Workspace (default: the module's).  On the current stream, no host
+    synchronisation.  Deterministic."""
+    who = "forward_sum_bwd"
+    g = _fsum_args(who, scores, q_len, key_len)
+    B, tq, tk = g.batch, g.tq, g.tk
+    if dscores is None and gamma is None:
+        raise ValueError(f"{who}: dscores or gamma is required")
+    if lse is None or alpha is None:
+        raise ValueError(f"{who}: lse and alpha are required")
+    if lse.dtype != torch.float32 or tuple(lse.shape) != (B, tq) or not lse.is_contiguous():
+        raise ValueError(f"{who}: lse must be a contiguous f32 [{B}, {tq}], got {lse.dtype} {tuple(lse.shape)}")
+    _fsum_alpha(who, g, alpha)
+    if dscores is not None:
+        g.d_ld, g.d_bs = _fsum_mat(who, "dscores", dscores, B, tq, tk, out=True)
+    if gamma is not None:
+        g.g_ld, g.g_bs = _fsum_mat(who, "gamma", gamma, B, tq, tk, out=True)
+    _vec(who, "grad_loss", grad_loss, B, torch.float32, exact=True, err=ValueError)
+    _same_gpu(who, (scores, lse, alpha, dscores, gamma, grad_loss, q_len, key_len), err=ValueError)
+    g.lse, g.grad_loss, g.dscores, g.gamma = lse.data_ptr(), ptr(grad_loss), ptr(dscores), ptr(gamma)
+    L = lib()
+    _bind_workspace(g, L.tt2_forward_sum_bwd_workspace_size(B, tq, tk), workspace)
+    check(L.tt2_forward_sum_bwd(C.byref(g), stream_ptr()), "tt2_forward_sum_bwd")
+    return dscores, gamma
+
+
+def forward_sum_path(scores, path, durations, logp, q_len=None, key_len=None, workspace=None):
+    """The best monotone path of a score matrix (tt2_forward_sum_path), the binarisation of the
+    forward-sum alignment: scores [B, Ty, Tx] f32 -> path [B, Ty] int32 (-1 past the utterance),
+    durations [B, Tx] int32 and logp [B] f32, the mean log-softmax along the path; the conventions are
+    align_monotonic's.  workspace: a Workspace (default: the module's).  On the current stream, no
+    host synchronisation.  Deterministic."""
+    who = "forward_sum_path"
+    g = _fsum_args(who, scores, q_len, key_len)
+    B, tq, tk = g.batch, g.tq, g.tk
+    for name, t, n in (("path", path, tq), ("durations", durations, tk)):
+        if t is None or t.dtype != torch.int32 or tuple(t.shape) != (B, n) or not t.is_contiguous():
+            raise ValueError(f"{who}: {name} must be a contiguous int32 [{B}, {n}]")
+    if logp is None:
+        raise ValueError(f"{who}: logp is required")
+    _vec(who, "logp", logp, B, torch.float32, exact=True, err=ValueError)
+    _same_gpu(who, (scores, path, durations, logp, q_len, key_len), err=ValueError)
+    g.path, g.durations, g.logp = path.data_ptr(), durations.data_ptr(), logp.data_ptr()
+    L = lib()
+    _bind_workspace(g, L.tt2_forward_sum_path_workspace_size(B, tq, tk), workspace)
+    check(L.tt2_forward_sum_path(C.byref(g), stream_ptr()), "tt2_forward_sum_path")
+    return path, durations, logp
 
 
 def _drop_into(s, drop: Drop):
