@@ -1,4 +1,5 @@
-"""Plain references of the HBM-bound kernels in csrc/misc.hip, written from the contracts in
+"""Plain references of the HBM-bound kernels in csrc/reduce.hip, embed.hip, loss.hip, optim.hip
+and repack.hip, written from the contracts in
 include/tt2_capi.h (not from the kernels).  Everything runs on the CPU in float64 unless a
 `dtype` is given: the same code in float32 is the yardstick of the non-exact checks
 (`worst_ratio`).  tests/test_misc_refs.py validates these against independent

@@ -1,4 +1,5 @@
-"""Plain references of the LayerNorm and BatchNorm kernels in csrc/norm.hip, written from the
+"""Plain references of the LayerNorm and BatchNorm kernels in csrc/layernorm.hip and
+csrc/batchnorm.hip, written from the
 contracts in include/tt2_capi.h (not from the kernels), and the exact-arithmetic problems of
 tests/test_gpu_norm_exact.py.  Everything runs on the CPU in float64 unless a `dtype` is given:
 the same code in float32 is the yardstick of the non-exact checks (`worst_ratio_by`).  No

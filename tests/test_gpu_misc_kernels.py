@@ -1,4 +1,5 @@
-"""Every kernel of csrc/misc.hip on its own against the float64 references of tests/_misc_refs.py
+"""Every kernel of csrc/reduce.hip, embed.hip, loss.hip, optim.hip and repack.hip on its own
+against the float64 references of tests/_misc_refs.py
 (validated on the CPU by tests/test_misc_refs.py), through tt2.ops (tt2_reduce_rows, which has
 no wrapper, through the C ABI).
 

@@ -1,4 +1,5 @@
-"""Every kernel of csrc/norm.hip against the float64 references of tests/_norm_refs.py (validated
+"""Every kernel of csrc/layernorm.hip and csrc/batchnorm.hip
+against the float64 references of tests/_norm_refs.py (validated
 on the CPU, with mutants, by tests/test_norm_refs.py), through the C ABI so that every field of
 tt2_ln_args / tt2_bn_args can be set (grad_beta, training = 0, out_dtype, res_dtype, stats_rows).
 

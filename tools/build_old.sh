@@ -1,10 +1,12 @@
 #!/bin/bash
 # abl/<name>.so: the current library with one source file as of commit <rev> (dev tool for
-# interleaved A/B via TT2_LIB).   tools/build_old.sh <name> <rev> <csrc file, e.g. norm.hip>
+# interleaved A/B via TT2_LIB).   tools/build_old.sh <name> <rev> <csrc file, e.g. batchnorm.hip>
 # The file must exist under the same name, with the same entry points, in both commits: a
 # revision from before gemm.hip was split into gemm_*.hip cannot be mixed in for the GEMM (its
 # gemm.hip defines what the gemm_*.o objects define too; the link reports duplicate symbols), and
-# likewise a revision from before attention.hip was split into attention_*.hip for the attention.
+# likewise a revision from before attention.hip was split into attention_*.hip for the attention,
+# or from before norm.hip and misc.hip were split (layernorm, batchnorm, reduce, embed, loss,
+# optim, repack, comm_standin) for those.
 # For that A/B build the old commit's whole library in a worktree.
 set -euo pipefail
 NAME=$1; REV=$2; FILE=$3

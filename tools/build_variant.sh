@@ -4,7 +4,7 @@
 # share headers and knobs, and TT2_PHASE changes the probe record width for the probe state and
 # every probed kernel alike, so they are recompiled together.  VAR_SRC names other sources
 # (base names, space separated).
-#   [VAR_SRC="norm attention"] tools/build_variant.sh <name> -DFOO=1 ...
+#   [VAR_SRC="layernorm batchnorm attention"] tools/build_variant.sh <name> -DFOO=1 ...
 set -euo pipefail
 NAME=$1; shift
 ROOT=$(cd "$(dirname "$0")/.." && pwd)

@@ -26,7 +26,7 @@ __device__ unsigned long long g_st[4096 * 64 * 4];
 #include "../transformer-tacotron2_amd/csrc/gemm_v10.hip"
 #include "../transformer-tacotron2_amd/csrc/gemm.hip"
 #include "../transformer-tacotron2_amd/csrc/runtime.cpp"
-// gemm_v7_impl.h's grouped launch sizes a LayerNorm finalize with this (norm.hip); unused here
+// gemm_v7_impl.h's grouped launch sizes a LayerNorm finalize with this (layernorm.hip); unused here
 extern "C" size_t tt2_layernorm_bwd_workspace_size(const tt2_ln_args*) { return 0; }
 
 int main(int argc, char** argv) {

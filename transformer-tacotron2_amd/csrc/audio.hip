@@ -18,10 +18,8 @@
 namespace {
 constexpr int NT = 256;
 
-int grid_for(int64_t total) {
-  const int64_t b = (total + NT - 1) / NT;
-  return (int)(b < 16384 ? (b > 0 ? b : 1) : 16384);
-}
+// tt2_common.h's grid_for with this file's cap of 16384 work groups
+int audio_grid(int64_t total) { return grid_for(total, NT, 16384); }
 
 // padded[b][j] = x[b][reflect(j - pad)] for j < len_b + 2 pad, 0 beyond (np.pad mode "reflect")
 __global__ void reflect_pad_kernel(const float* x, int64_t ldx, const int32_t* lens, int B, int L, float* out,
@@ -149,7 +147,7 @@ extern "C" int tt2_reflect_pad(const float* x, int64_t ldx, const int32_t* lens,
   if (padded_len < (int64_t)len + 2 * (int64_t)pad)
     return tt2_set_error(TT2_E_INVALID, "tt2_reflect_pad: padded_len short");
   if (batch > 1 && ldx < len) return tt2_set_error(TT2_E_INVALID, "tt2_reflect_pad: ldx < len");
-  hipLaunchKernelGGL(reflect_pad_kernel, dim3(grid_for((int64_t)batch * padded_len)), dim3(NT), 0, s, x, ldx, lens,
+  hipLaunchKernelGGL(reflect_pad_kernel, dim3(audio_grid((int64_t)batch * padded_len)), dim3(NT), 0, s, x, ldx, lens,
                      batch, len, out, padded_len, pad);
   return tt2_check_launch(hipGetLastError(), "tt2_reflect_pad");
 }
@@ -158,7 +156,7 @@ extern "C" int tt2_spec_magnitude(const float* spec, int64_t ld_spec, int32_t m,
                                   int64_t ld_mag, hipStream_t s) {
   if (!spec || !mag || m <= 0 || ld_spec < 2 * n_bins || ld_mag < n_bins)
     return tt2_set_error(TT2_E_INVALID, "tt2_spec_magnitude: bad args");
-  hipLaunchKernelGGL(spec_mag_kernel, dim3(grid_for((int64_t)m * ld_mag)), dim3(NT), 0, s, spec, ld_spec, m, n_bins,
+  hipLaunchKernelGGL(spec_mag_kernel, dim3(audio_grid((int64_t)m * ld_mag)), dim3(NT), 0, s, spec, ld_spec, m, n_bins,
                      mag, ld_mag);
   return tt2_check_launch(hipGetLastError(), "tt2_spec_magnitude");
 }
@@ -168,7 +166,7 @@ extern "C" int tt2_spec_rephase(const float* mag, int64_t ld_mag, const float* e
   if (!mag || !out || m <= 0 || ld_mag < n_bins || ld_out < 2 * n_bins || ld_out > 3 * n_bins ||
       (est && ld_est < 2 * n_bins))
     return tt2_set_error(TT2_E_INVALID, "tt2_spec_rephase: bad args");
-  hipLaunchKernelGGL(spec_rephase_kernel, dim3(grid_for((int64_t)m * n_bins)), dim3(NT), 0, s, mag, ld_mag, est,
+  hipLaunchKernelGGL(spec_rephase_kernel, dim3(audio_grid((int64_t)m * n_bins)), dim3(NT), 0, s, mag, ld_mag, est,
                      ld_est, m, n_bins, out, ld_out);
   return tt2_check_launch(hipGetLastError(), "tt2_spec_rephase");
 }
@@ -179,7 +177,7 @@ extern "C" int tt2_overlap_add(const float* frames, int64_t ld_frames, const int
   if (!frames || !y || batch <= 0 || len <= 0 || hop <= 0 || n_fft < hop || ld_frames < n_fft ||
       (int64_t)rows_per_utt * hop < (int64_t)len + n_fft || (batch > 1 && ld_y < len))
     return tt2_set_error(TT2_E_INVALID, "tt2_overlap_add: bad args");
-  hipLaunchKernelGGL(overlap_add_kernel, dim3(grid_for((int64_t)batch * len)), dim3(NT), 0, s, frames, ld_frames,
+  hipLaunchKernelGGL(overlap_add_kernel, dim3(audio_grid((int64_t)batch * len)), dim3(NT), 0, s, frames, ld_frames,
                      lens, batch, len, rows_per_utt, n_fft, hop, n_fft / 2, y, ld_y);
   return tt2_check_launch(hipGetLastError(), "tt2_overlap_add");
 }
@@ -190,7 +188,7 @@ extern "C" int tt2_mel_rows(float* rows, int64_t ld_rows, float* mel, const int3
   if (!rows || !mel || batch <= 0 || t <= 0 || t > rows_per_utt || n_mels <= 0 || ld_rows < n_mels ||
       !(clamp > 0.f))
     return tt2_set_error(TT2_E_INVALID, "tt2_mel_rows: bad args");
-  hipLaunchKernelGGL(mel_rows_kernel, dim3(grid_for((int64_t)batch * rows_per_utt * n_mels)), dim3(NT), 0, s, rows,
+  hipLaunchKernelGGL(mel_rows_kernel, dim3(audio_grid((int64_t)batch * rows_per_utt * n_mels)), dim3(NT), 0, s, rows,
                      ld_rows, mel, frames, batch, t, n_mels, rows_per_utt, clamp, scatter ? 1 : 0);
   return tt2_check_launch(hipGetLastError(), "tt2_mel_rows");
 }

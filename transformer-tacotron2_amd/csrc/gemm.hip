@@ -228,7 +228,7 @@ int tt2g::gemm_prep(const tt2_gemm_args* a, Operand& A, Operand& B, Epilogue& ep
   ep.res = a->res; ep.ldr = a->ldr; ep.res_dt = a->res_dtype;
   ep.gate = a->gate; ep.ldg = a->ldg; ep.gate_dt = a->gate_dtype; ep.gate_scale = a->gate_scale;
   ep.alpha = a->alpha; ep.beta = a->beta; ep.act = a->act;
-  ep.drop = DropDesc{a->drop_seed, a->drop_site, a->drop_thr, a->drop_scale};
+  ep.drop = drop_of(a);
   if (ep.drop.thr && !ep.drop.seed) return tt2_set_error(TT2_E_INVALID, "tt2_gemm: dropout without seed");
   ep.n_log = a->n;
   ep.ksum = a->a_ksum;
@@ -243,7 +243,7 @@ int tt2g::gemm_prep(const tt2_gemm_args* a, Operand& A, Operand& B, Epilogue& ep
     ep.bnb.y = reinterpret_cast<const bf16*>(bn->y);
     ep.bnb.mean = bn->mean; ep.bnb.rstd = bn->rstd; ep.bnb.gamma = bn->gamma; ep.bnb.beta = bn->beta;
     ep.bnb.part = reinterpret_cast<float*>(bn->workspace);
-    ep.bnb.drop = DropDesc{bn->drop_seed, bn->drop_site, bn->drop_thr, bn->drop_scale};
+    ep.bnb.drop = drop_of(bn);
     ep.bnb.act = bn->act;
   }
   ep.vec = epi_vec_ok(a);

@@ -173,6 +173,37 @@ template <typename T> TT2_DEV void ld8f(const T* p, float (&v)[8]) {
     for (int j = 0; j < 8; ++j) v[j] = (float)x[j];
   }
 }
+// 8 f32 values to 8 consecutive elements
+template <typename T> TT2_DEV void st8(T* p, const float (&v)[8]);
+template <> TT2_DEV void st8(bf16* p, const float (&v)[8]) {
+  bf16x8 x;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) x[j] = (bf16)v[j];
+  *reinterpret_cast<bf16x8*>(p) = x;
+}
+template <> TT2_DEV void st8(f16* p, const float (&v)[8]) {
+  f16x8 x;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) x[j] = (f16)v[j];
+  *reinterpret_cast<f16x8*>(p) = x;
+}
+template <> TT2_DEV void st8(float* p, const float (&v)[8]) {
+  *reinterpret_cast<f32x4*>(p) = f32x4{v[0], v[1], v[2], v[3]};
+  *reinterpret_cast<f32x4*>(p + 4) = f32x4{v[4], v[5], v[6], v[7]};
+}
+// Nontemporal form for the training kernels' full-tensor outputs: the rows stream out as
+// they are produced instead of sitting dirty in L2 until the end-of-kernel write-back.
+template <typename T> TT2_DEV void st8nt(T* p, const float (&v)[8]) {
+  if constexpr (sizeof(T) == 4) {
+    __builtin_nontemporal_store(f32x4{v[0], v[1], v[2], v[3]}, reinterpret_cast<f32x4*>(p));
+    __builtin_nontemporal_store(f32x4{v[4], v[5], v[6], v[7]}, reinterpret_cast<f32x4*>(p) + 1);
+  } else {
+    T x[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) x[j] = (T)v[j];
+    __builtin_nontemporal_store(*reinterpret_cast<const u32x4*>(x), reinterpret_cast<u32x4*>(p));
+  }
+}
 
 // The decode step's residual combine + LayerNorm of one 512-wide row by one wave (lane =
 // 8-column chunk c0 = 8 lane): y = LN(x + (bias + sum_s part[s])) with the slab sum in fixed
@@ -247,4 +278,25 @@ TT2_DEV float act_f(int act, float v) {
 }
 TT2_DEV float act_grad_from_out(int act, float z) {
   return act == ACT_RELU ? (z > 0.f ? 1.f : 0.f) : (act == ACT_TANH ? 1.f - z * z : 1.f);
+}
+
+// ---------------------------------------------------------------- host side of a launch
+// work groups of a grid-stride kernel over `total` items, `per` to a work group: 1 .. cap
+inline int grid_for(int64_t total, int per = 256, int cap = 8192) {
+  const int64_t b = (total + per - 1) / per;
+  return (int)(b < cap ? (b > 0 ? b : 1) : cap);
+}
+// The storage type of a launch: f(T()) with T = bf16 for a C-ABI dtype of TT2_DT_BF16 (= TT2_BF16),
+// float for any other; by_dtype2: f(T(), TD()) for an (element, gradient) pair of dtypes.
+//   by_dtype(p->dtype, [&](auto t) { hipLaunchKernelGGL(kernel<decltype(t)>, ...); });
+template <typename F> void by_dtype(int dtype, F&& f) {
+  if (dtype == TT2_BF16) f(bf16());
+  else f(float());
+}
+template <typename F> void by_dtype2(int dtype, int grad_dtype, F&& f) {
+  by_dtype(dtype, [&](auto t) { by_dtype(grad_dtype, [&](auto td) { f(t, td); }); });
+}
+// the dropout descriptor of a C-ABI argument struct (its four drop_* fields)
+template <typename A> DropDesc drop_of(const A* p) {
+  return DropDesc{p->drop_seed, p->drop_site, p->drop_thr, p->drop_scale};
 }
