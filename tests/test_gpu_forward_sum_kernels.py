@@ -28,7 +28,9 @@ from tt2 import _lib  # noqa: E402
 
 GUARD = 64
 SENT = -77
-PATH_SHAPES = F.SHAPES + [(300, 260)]      # + a shape whose move bits go to the workspace
+# + the shapes whose move bits go to the workspace: more than 256 frames at the 512-key capacity,
+# more than 1536 at the 256-key one (F.SHAPES holds each capacity with the bits in LDS)
+PATH_SHAPES = F.SHAPES + [(300, 260), (1540, 130)]
 
 
 def bits(x):

@@ -60,6 +60,9 @@ EXACT = [
     # every lane's key run at the largest tk
     (_lib.MONO_MAX_KEYS + 8, _lib.MONO_MAX_KEYS, [_lib.MONO_MAX_KEYS + 8, _lib.MONO_MAX_KEYS],
      [_lib.MONO_MAX_KEYS, _lib.MONO_MAX_KEYS - 1], [(0, 1), (1, 0)]),
+    # the 512-key capacity with the move bits in LDS (at most 256 frames; the case above and
+    # test_move_bits_in_the_workspace hold the two capacities whose bits go to the workspace)
+    (40, 300, [40, 33], [300, 270], [(0, 1), (1, 0)]),
 ]
 REAL = [
     (65, 129, None, None, [(1, 1), (0, 0)]),

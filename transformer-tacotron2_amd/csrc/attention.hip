@@ -20,11 +20,11 @@ int validate(const tt2_attn_args* p) {
 
 // guided launches: non-causal only (the loss is defined on encoder-decoder attention)
 int check_guide(const tt2_attn_args* p, const tt2_attn_guide* g, bool bwd, const char* who) {
-  if (!g) return attn_err(who, "guide required");
-  if (p->causal) return attn_err(who, "guided attention is non-causal only");
-  if (!g->rows || (bwd && !g->coef)) return attn_err(who, "guide rows / coef required");
+  if (!g) return tt2_invalid(who, "guide required");
+  if (p->causal) return tt2_invalid(who, "guided attention is non-causal only");
+  if (!g->rows || (bwd && !g->coef)) return tt2_invalid(who, "guide rows / coef required");
   if (!(g->sigma > 0.f) || g->heads < 0 || g->heads > p->heads)
-    return attn_err(who, "guide needs sigma > 0 and 0 <= heads <= the attention's heads");
+    return tt2_invalid(who, "guide needs sigma > 0 and 0 <= heads <= the attention's heads");
   return TT2_OK;
 }
 
@@ -47,7 +47,7 @@ int v3_waves(const tt2_attn_args* p, int rows, bool fwd) {
 
 int attn_fwd(const tt2_attn_args* p, const tt2_attn_guide* g, bool guided, hipStream_t s, const char* who) {
   if (int rc = validate(p)) return rc;
-  if (!p->o_out || !p->lse) return attn_err(who, "out/lse required");
+  if (!p->o_out || !p->lse) return tt2_invalid(who, "out/lse required");
   if (guided)
     if (int rc = check_guide(p, g, false, who)) return rc;
   if (p->batch * p->tq == 0) return TT2_OK;
@@ -60,7 +60,7 @@ int attn_fwd(const tt2_attn_args* p, const tt2_attn_guide* g, bool guided, hipSt
 int attn_bwd(const tt2_attn_args* p, const tt2_attn_guide* g, bool guided, hipStream_t s, const char* who) {
   if (int rc = validate(p)) return rc;
   if (!p->dq || !p->dk || !p->dv || !p->delta || !p->lse || !p->o || !p->dout)
-    return attn_err(who, "missing buffer");
+    return tt2_invalid(who, "missing buffer");
   if (guided)
     if (int rc = check_guide(p, g, true, who)) return rc;
   if (p->batch * p->tq == 0) return TT2_OK;
@@ -76,7 +76,7 @@ int attn_bwd(const tt2_attn_args* p, const tt2_attn_guide* g, bool guided, hipSt
     return tt2_check_launch(hipGetLastError(), who);
   }
   if (p->parts != 0)
-    return attn_err(who, p->dtype == TT2_DT_BF16 ? "parts needs the non-causal bf16 launch (4-wave v3)" : "parts needs bf16");
+    return tt2_invalid(who, p->dtype == TT2_DT_BF16 ? "parts needs the non-causal bf16 launch (4-wave v3)" : "parts needs bf16");
   if (nq == 0) launch_bwd_prep1(p, g, s);
   if (nq) launch_bwd_dq3(p, g, nq, s);
   else launch_bwd_dq1(p, g, s);
@@ -113,13 +113,13 @@ extern "C" int tt2_attn_probs(const tt2_attn_args* p, float* probs, hipStream_t 
 
 extern "C" int tt2_guided_attn_loss(const tt2_guide_loss_args* p, hipStream_t s) {
   const char* who = "tt2_guided_attn_loss";
-  if (!p || !p->term || !p->coef) return attn_err(who, "term / coef required");
-  if (p->n_layers < 0 || p->n_layers > TT2_GUIDE_MAX_LAYERS) return attn_err(who, "too many layers");
+  if (!p || !p->term || !p->coef) return tt2_invalid(who, "term / coef required");
+  if (p->n_layers < 0 || p->n_layers > TT2_GUIDE_MAX_LAYERS) return tt2_invalid(who, "too many layers");
   if (p->batch < 0 || p->tq < 0 || p->tk < 0 || p->heads <= 0 || p->guide_heads < 0 || p->guide_heads > p->heads ||
       (int64_t)p->heads * p->tq > INT32_MAX)
-    return attn_err(who, "shape");
+    return tt2_invalid(who, "shape");
   for (int l = 0; l < p->n_layers; ++l)
-    if (!p->rows[l]) return attn_err(who, "rows buffer missing");
+    if (!p->rows[l]) return tt2_invalid(who, "rows buffer missing");
   bool vec = ((int64_t)p->guide_heads * p->tq) % 4 == 0 && ((int64_t)p->heads * p->tq) % 4 == 0;
   for (int l = 0; l < p->n_layers; ++l) vec = vec && reinterpret_cast<uintptr_t>(p->rows[l]) % 16 == 0;
   launch_guide_loss(p, vec, s);
@@ -128,44 +128,44 @@ extern "C" int tt2_guided_attn_loss(const tt2_guide_loss_args* p, hipStream_t s)
 
 extern "C" int tt2_attn_align(const tt2_align_args* p, hipStream_t s) {
   const char* who = "tt2_attn_align";
-  if (!p) return attn_err(who, "args required");
-  if (p->head_dim != D) return attn_err(who, "head_dim must be 64");
-  if (p->causal) return attn_err(who, "alignment statistics are non-causal only");
-  if (p->n_layers < 0 || p->n_layers > TT2_GUIDE_MAX_LAYERS) return attn_err(who, "too many layers");
-  if (p->dtype != TT2_DT_BF16 && p->dtype != TT2_DT_F32) return attn_err(who, "dtype must be bf16 or f32");
+  if (!p) return tt2_invalid(who, "args required");
+  if (p->head_dim != D) return tt2_invalid(who, "head_dim must be 64");
+  if (p->causal) return tt2_invalid(who, "alignment statistics are non-causal only");
+  if (p->n_layers < 0 || p->n_layers > TT2_GUIDE_MAX_LAYERS) return tt2_invalid(who, "too many layers");
+  if (p->dtype != TT2_DT_BF16 && p->dtype != TT2_DT_F32) return tt2_invalid(who, "dtype must be bf16 or f32");
   if (p->batch < 0 || p->heads <= 0 || p->tq < 0 || p->tk < 0 || !(p->scale > 0.f) ||
       (int64_t)p->batch * p->heads > INT32_MAX)
-    return attn_err(who, "shape / scale");
+    return tt2_invalid(who, "shape / scale");
   const int esz = p->dtype == TT2_DT_BF16 ? 2 : 4;
   if ((p->q_ld * esz) % 16 || (p->k_ld * esz) % 16 || p->q_ld < (int64_t)p->heads * D || p->k_ld < (int64_t)p->heads * D)
-    return attn_err(who, "leading dims must be 16-B multiples covering the heads");
-  if (!p->pmax || !p->amax) return attn_err(who, "pmax / amax required");
+    return tt2_invalid(who, "leading dims must be 16-B multiples covering the heads");
+  if (!p->pmax || !p->amax) return tt2_invalid(who, "pmax / amax required");
   for (int l = 0; l < p->n_layers; ++l)
-    if (!p->q[l] || !p->k[l] || !p->lse[l]) return attn_err(who, "q / k / lse of a layer missing");
+    if (!p->q[l] || !p->k[l] || !p->lse[l]) return tt2_invalid(who, "q / k / lse of a layer missing");
   if (p->n_layers == 0 || p->batch == 0 || p->tq == 0) return TT2_OK;
   const int BH = p->batch * p->heads;
   // the forward's rule: four waves share each K tile while that still fills the chip
   const int nw = v3_waves(p->dtype, p->variant, p->tq, (int64_t)BH * p->n_layers, true);
   // the v3 kernel's buffer views address rows with 32-bit byte offsets
   if (nw && (((int64_t)p->tq * p->q_ld + D) * 2 > INT32_MAX || ((int64_t)p->tk * p->k_ld + D) * 2 > INT32_MAX))
-    return attn_err(who, "one batch element's q or k spans more than 2 GiB");
-  if (!nw && BH > 65535) return attn_err(who, "the plain kernel takes at most 65535 (batch, head) pairs");
+    return tt2_invalid(who, "one batch element's q or k spans more than 2 GiB");
+  if (!nw && BH > 65535) return tt2_invalid(who, "the plain kernel takes at most 65535 (batch, head) pairs");
   launch_align(p, nw, s);
   return tt2_check_launch(hipGetLastError(), who);
 }
 
 extern "C" int tt2_align_durations(const tt2_align_dur_args* p, hipStream_t s) {
   const char* who = "tt2_align_durations";
-  if (!p) return attn_err(who, "args required");
+  if (!p) return tt2_invalid(who, "args required");
   if (!p->pmax || !p->amax || !p->focus || !p->sel || !p->sel_focus || !p->durations)
-    return attn_err(who, "missing buffer");
-  if (p->n_layers <= 0 || p->n_layers > TT2_GUIDE_MAX_LAYERS) return attn_err(who, "needs 1..16 layers");
+    return tt2_invalid(who, "missing buffer");
+  if (p->n_layers <= 0 || p->n_layers > TT2_GUIDE_MAX_LAYERS) return tt2_invalid(who, "needs 1..16 layers");
   if (p->batch < 0 || p->heads <= 0 || p->tq < 0 || p->tk < 0 ||
       (int64_t)p->n_layers * p->heads > ALIGN_DUR_MAX_PAIRS)
-    return attn_err(who, "shape");
-  if (p->mode != 0 && p->mode != 1) return attn_err(who, "mode must be 0 (best head) or 1 (fixed head)");
+    return tt2_invalid(who, "shape");
+  if (p->mode != 0 && p->mode != 1) return tt2_invalid(who, "mode must be 0 (best head) or 1 (fixed head)");
   if (p->mode == 1 && (p->sel_layer < 0 || p->sel_layer >= p->n_layers || p->sel_head < 0 || p->sel_head >= p->heads))
-    return attn_err(who, "fixed head outside the layers / heads");
+    return tt2_invalid(who, "fixed head outside the layers / heads");
   if (p->batch == 0) return TT2_OK;
   launch_align_dur(p, s);
   return tt2_check_launch(hipGetLastError(), who);

@@ -17,7 +17,7 @@
 // A family keeps its kernels in an anonymous namespace and exports host launchers (namespace tt2a,
 // below) that take the C-ABI structs and plain scalars, so no unit refers to another unit's kernels
 // (no relocatable device code).  Here: the tile constants, the kernels' argument structs and their
-// conversion from the C ABI, the length clamp, the guided-attention weight, the error helper.
+// conversion from the C ABI, the key limit, the guided-attention weight.
 //
 // Backward (no atomics, bitwise reproducible): a dQ kernel walks key tiles per query block, a
 // dK/dV kernel walks query tiles per key block; both recompute P from the saved LSE (log2 domain,
@@ -27,7 +27,6 @@
 #pragma once
 #include <math.h>
 
-#include <string>
 #include <type_traits>
 
 #include "tt2_capi.h"
@@ -112,19 +111,9 @@ template <typename F> void with_args(const tt2_attn_args* p, const tt2_attn_guid
   else f(std::false_type{}, to_args<false>(p));
 }
 
-inline int attn_err(const char* who, const char* msg) {
-  return tt2_set_error(TT2_E_INVALID, (std::string(who) + ": " + msg).c_str());
-}
-
-// rows of batch element b that count: T, cut to the per-batch length (NULL: none), never negative
-TT2_DEV int len_limit(int T, const int32_t* len, int b) {
-  int l = T;
-  if (len) l = min(l, len[b]);
-  return l < 0 ? 0 : l;
-}
-// the visible keys of batch element b.  (Taking the arguments by reference is deliberate: with
-// len_limit called on a.Tk / a.key_len at the call sites, the plain v1 forward, dQ and probs
-// kernels compiled to different code.)
+// the visible keys of batch element b (len_limit: tt2_common.h).  (Taking the arguments by
+// reference is deliberate: with len_limit called on a.Tk / a.key_len at the call sites, the plain
+// v1 forward, dQ and probs kernels compiled to different code.)
 TT2_DEV int key_limit(const AttnArgs& a, int b) { return len_limit(a.Tk, a.key_len, b); }
 
 // Guided attention (diagonal loss on the cross-attention, G instantiations): the weight of

@@ -3,7 +3,6 @@
 // unit of its own: no other kernel's code depends on it.
 #include <math.h>
 
-#include <string>
 
 #include "tt2_capi.h"
 #include "tt2_internal.h"
@@ -286,7 +285,7 @@ __global__ __launch_bounds__(DTW_NT) void dtw_kernel(tt2_dtw_args a) {
   }
 }
 
-int dtw_err(const char* msg) { return tt2_set_error(TT2_E_INVALID, (std::string("tt2_dtw: ") + msg).c_str()); }
+int dtw_err(const char* msg) { return tt2_invalid("tt2_dtw", msg); }
 
 template <int CPL>
 void dtw_launch(const tt2_dtw_args& a, int nf, hipStream_t s) {
@@ -312,9 +311,9 @@ extern "C" int tt2_dtw(const tt2_dtw_args* p, hipStream_t s) {
   if (p->batch == 0) return TT2_OK;   // nothing to write: the arrays of an empty batch may be null
   if (!p->total || !p->length) return dtw_err("total / length required");
   const bool want = p->path_a != nullptr;
-  const size_t need = tt2_dtw_workspace_size(p->batch, p->ta, p->tb, want);
-  if (need && (!p->workspace || p->workspace_bytes < need || (reinterpret_cast<uintptr_t>(p->workspace) & 3)))
-    return dtw_err(("workspace too small or misaligned: " + std::to_string(need) + " bytes needed").c_str());
+  const int rc = tt2_need_workspace("tt2_dtw", p->workspace, p->workspace_bytes,
+                                    tt2_dtw_workspace_size(p->batch, p->ta, p->tb, want), 4);
+  if (rc != TT2_OK) return rc;
   if (p->ta > 0 && p->tb > 0 && (!p->a || !p->b)) return dtw_err("a / b required");
   if (dtw_cpl(p->tb) == 1) dtw_launch<1>(*p, nf, s);
   else dtw_launch<2>(*p, nf, s);

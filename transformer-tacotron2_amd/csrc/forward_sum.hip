@@ -2,9 +2,9 @@
 // probability of all monotone alignments (tt2_forward_sum_fwd), its gradient and posterior
 // (tt2_forward_sum_bwd) and its best path (tt2_forward_sum_path).  tt2_capi.h states the
 // definition.  A translation unit of its own: no other kernel's code depends on it.  The launch
-// shape is align_mono_kernel's (attention_mono.hip): one work group per utterance, FS_NP producer
-// waves form 32-row blocks into double-buffered LDS while one wave walks the recurrence with a
-// contiguous run of keys per lane and takes its neighbour's value by a DPP wave shift.
+// shape is align_walk.h's: one work group per utterance, WALK_NP producer waves form 32-row blocks
+// into double-buffered LDS while one wave walks the recurrence with a contiguous run of keys per
+// lane and takes its neighbour's value by a DPP wave shift.
 //
 //   fsum_walk_kernel<KC, DIR>   DIR 0: the alpha pass.  The producers form ls = s - lse (the row
 //                               log-sum-exp is theirs and goes to `lse`); the walker adds in log
@@ -15,22 +15,17 @@
 //                               logaddexp before the row's ls is added) in walk order.
 //   fsum_grad_kernel            a wave per row: gamma = softmax_t(alpha + beta), P = exp(s - lse),
 //                               dscores = grad_loss * (P - gamma), +0 in the padding.
-//   fsum_path_kernel<KC>        align_mono_kernel's walker, ballots and backtrack over the raw scores.
+//   fsum_path_kernel<KC>        the best path: align_walk.h's Viterbi walk over the raw scores, the
+//                               backtrack over its move bits, then ls along the path.
 #include <limits.h>
 #include <math.h>
 
-#include <string>
-#include <type_traits>
-
 #include "tt2_capi.h"
 #include "tt2_internal.h"
-#include "tt2_common.h"
+#include "align_walk.h"
 
 namespace {
 
-constexpr int FS_NP = 4;                    // producer waves
-constexpr int FS_NT = 64 * (FS_NP + 1);     // + the walker
-constexpr int FS_RB = 32;                   // rows per block
 constexpr float FS_NEG = -1e30f;            // a cell no path reaches (finite: NEG - NEG is 0, not NaN)
 constexpr int FS_GRAD_ROWS = 4;             // fsum_grad_kernel: rows (waves) per work group
 // rows between two renormalisations of the walker (a build knob for the measurement in DESIGN.md 5.14;
@@ -38,26 +33,6 @@ constexpr int FS_GRAD_ROWS = 4;             // fsum_grad_kernel: rows (waves) pe
 #ifndef FS_RENORM
 #define FS_RENORM 1
 #endif
-
-template <int KC> struct FsCfg {            // KC: key capacity (tk rounded up)
-  static constexpr int R = KC / 64;         // keys per walker lane
-  static constexpr int NK = KC / 64;        // keys per producer lane (strided by 64)
-  static constexpr int SLD = KC + 4;        // LDS row stride in floats
-  static constexpr int SBUF = (FS_RB + 1) * SLD;   // + a row the walker's look-ahead may read
-  static constexpr int MOVE_BYTES = KC == 128 ? 65536 : KC == 256 ? 49152 : 16384;   // path: move bits in LDS
-};
-__host__ __device__ constexpr int fs_kc(int tk) { return tk <= 128 ? 128 : tk <= 256 ? 256 : 512; }
-__host__ __device__ inline size_t fs_move_bytes(int tq, int tk) { return (size_t)tq * (fs_kc(tk) / 64) * 8; }
-__host__ __device__ inline bool fs_move_in_lds(int tq, int tk) {
-  const int kc = fs_kc(tk);
-  return fs_move_bytes(tq, tk) <= (size_t)(kc == 128 ? 65536 : kc == 256 ? 49152 : 16384);
-}
-
-TT2_DEV int fs_len(int T, const int32_t* len, int b) {
-  int l = T;
-  if (len) l = min(l, len[b]);
-  return l < 0 ? 0 : l;
-}
 
 // wave_sum's lane pattern with max
 TT2_DEV float fs_wave_max(float v) {
@@ -77,11 +52,10 @@ TT2_DEV float fs_wave_max(float v) {
 // is about 2^-24, the rounding of the sum itself once |m| reaches 1/2; ocml's expf and log1pf in its
 // place measured 607 ns a row against this form's figure in DESIGN.md 5.14.
 constexpr float FS_LOG2E = 1.4426950408889634f;
-constexpr float FS_LN2 = 0.6931471805599453f;
 TT2_DEV float fs_lae(float a, float b) {
   const float m = fmaxf(a, b);
   const float e = __builtin_amdgcn_exp2f((fminf(a, b) - m) * FS_LOG2E);
-  const float r = e < 0x1p-12f ? e * (1.f - 0.5f * e) : FS_LN2 * __builtin_amdgcn_logf(1.f + e);
+  const float r = e < 0x1p-12f ? e * (1.f - 0.5f * e) : LN2 * __builtin_amdgcn_logf(1.f + e);
   return m + r;
 }
 
@@ -105,18 +79,7 @@ template <int NK> TT2_DEV float fs_row_lse(int Tx, int lane, const float (&x)[NK
   return logf(wave_sum(sum));
 }
 
-template <int R> TT2_DEV void fs_ld_row(float (&s)[R], const float* p) {
-  if constexpr (R == 2) {
-    const float2 x = *reinterpret_cast<const float2*>(p);
-    s[0] = x.x; s[1] = x.y;
-  } else {
-#pragma unroll
-    for (int q = 0; q < R / 4; ++q) {
-      const float4 x = *reinterpret_cast<const float4*>(p + 4 * q);
-      s[4 * q] = x.x; s[4 * q + 1] = x.y; s[4 * q + 2] = x.z; s[4 * q + 3] = x.w;
-    }
-  }
-}
+// a lane's R consecutive floats to a row (walk_ld_row's counterpart)
 template <int R> TT2_DEV void fs_st_row(float* p, const float (&s)[R]) {
   if constexpr (R == 2) {
     *reinterpret_cast<float2*>(p) = make_float2(s[0], s[1]);
@@ -130,20 +93,20 @@ template <int R> TT2_DEV void fs_st_row(float* p, const float (&s)[R]) {
 // Walk row m and walk key p are frame m and key p for DIR 0, frame Ty - 1 - m and key Te - 1 - p
 // for DIR 1; keys at and past Te keep their place.
 template <int KC, int DIR>
-__global__ __launch_bounds__(FS_NT) void fsum_walk_kernel(tt2_forward_sum_args a) {
-  using C = FsCfg<KC>;
+__global__ __launch_bounds__(WALK_NT) void fsum_walk_kernel(tt2_forward_sum_args a) {
+  using C = WalkCfg<KC>;
   constexpr int R = C::R, NK = C::NK, SLD = C::SLD, SBUF = C::SBUF;
   __shared__ __attribute__((aligned(16))) float sS[2 * SBUF];
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const int b = blockIdx.x;
-  const int Ty = fs_len(a.tq, a.q_len, b);
-  const int Tx = fs_len(a.tk, a.key_len, b);
+  const int Ty = len_limit(a.tq, a.q_len, b);
+  const int Tx = len_limit(a.tk, a.key_len, b);
   const int Te = min(Tx, Ty);
   float* lse = a.lse + (int64_t)b * a.tq;
   if constexpr (DIR == 0) {
-    for (int n = Ty + tid; n < a.tq; n += FS_NT) lse[n] = 0.f;
+    for (int n = Ty + tid; n < a.tq; n += WALK_NT) lse[n] = 0.f;
     if (Ty <= 0 || Tx <= 0) {   // block-uniform
-      for (int n = tid; n < Ty; n += FS_NT) lse[n] = 0.f;
+      for (int n = tid; n < Ty; n += WALK_NT) lse[n] = 0.f;
       if (tid == 0) a.loss[b] = 0.f;
       return;
     }
@@ -153,21 +116,21 @@ __global__ __launch_bounds__(FS_NT) void fsum_walk_kernel(tt2_forward_sum_args a
   const float* sc = a.scores + (int64_t)b * a.s_bs;
   float* out = DIR == 0 ? (a.alpha ? a.alpha + (int64_t)b * a.tq * a.a_ld : nullptr)
                         : static_cast<float*>(a.workspace) + (int64_t)b * a.tq * KC;
-  const int nblk = (Ty + FS_RB - 1) / FS_RB;
+  const int nblk = (Ty + WALK_RB - 1) / WALK_RB;
 
   // ---- rows of block i -> buffer i & 1 (producer waves, a wave per row)
   auto produce = [&](int i) {
     float* S = sS + (i & 1) * SBUF;
-    constexpr int PR = FS_RB / FS_NP;   // rows per producer wave, their loads issued together
+    constexpr int PR = WALK_RB / WALK_NP;   // rows per producer wave, their loads issued together
     float x[PR][NK];
 #pragma unroll
     for (int q = 0; q < PR; ++q) {
-      const int m = FS_RB * i + w + FS_NP * q;
+      const int m = WALK_RB * i + w + WALK_NP * q;
       if (m < Ty) fs_row_load<NK>(sc + (int64_t)(DIR ? Ty - 1 - m : m) * a.s_ld, Tx, lane, x[q]);
     }
 #pragma unroll
     for (int q = 0; q < PR; ++q) {
-      const int r = w + FS_NP * q, m = FS_RB * i + r;
+      const int r = w + WALK_NP * q, m = WALK_RB * i + r;
       if (m >= Ty) break;
       const int n = DIR ? Ty - 1 - m : m;
       float mx;
@@ -213,7 +176,6 @@ __global__ __launch_bounds__(FS_NT) void fsum_walk_kernel(tt2_forward_sum_args a
   };
   auto consume = [&](int i) {
     const float* S = sS + (i & 1) * SBUF + lane * R;
-    const int m0 = FS_RB * i, m1 = min(m0 + FS_RB, Ty);
     auto row = [&](const float (&s)[R], int m) {
       // the value at p - 1 of the lane's first key: the last key of the lane below (wave_shr:1)
       const float below = __int_as_float(__builtin_amdgcn_update_dpp(
@@ -226,34 +188,21 @@ __global__ __launch_bounds__(FS_NT) void fsum_walk_kernel(tt2_forward_sum_args a
       }
       finish(nv, lab, m);
     };
-    float sa[R], sb[R];
-    fs_ld_row<R>(sa, S);
-    int m = m0;
-    if (i == 0) {   // walk row 0: only walk key 0 can be reached
+    auto row0 = [&](const float (&s)[R]) {   // walk row 0: only walk key 0 can be reached
       float nv[R], lab[R];
 #pragma unroll
       for (int j = 0; j < R; ++j) {
         const bool first = lane == 0 && j == 0;
-        nv[j] = first ? sa[0] : FS_NEG;
+        nv[j] = first ? s[0] : FS_NEG;
         lab[j] = first ? 0.f : FS_NEG;
       }
       finish(nv, lab, 0);
-      fs_ld_row<R>(sa, S + SLD);
-      m = 1;
-    }
-    // two rows per trip, two register sets: each row is read one row ahead of the chain (after the
-    // block's last row the read falls on the buffer's spare row)
-    for (; m + 1 < m1; m += 2) {
-      fs_ld_row<R>(sb, S + (m + 1 - m0) * SLD);
-      row(sa, m);
-      fs_ld_row<R>(sa, S + (m + 2 - m0) * SLD);
-      row(sb, m + 1);
-    }
-    if (m < m1) row(sa, m);
+    };
+    walk_rows<R, SLD>(S, i, Ty, row0, row);
   };
 
   for (int i = 0; i <= nblk; ++i) {
-    if (w < FS_NP) {
+    if (w < WALK_NP) {
       if (i < nblk) produce(i);
     } else if (i > 0) {
       consume(i - 1);
@@ -262,7 +211,7 @@ __global__ __launch_bounds__(FS_NT) void fsum_walk_kernel(tt2_forward_sum_args a
   }
 
   if constexpr (DIR == 0) {
-    if (w == FS_NP) {   // ln Z = the offsets + the last row's value at key Te - 1
+    if (w == WALK_NP) {   // ln Z = the offsets + the last row's value at key Te - 1
       const int p = Te - 1;
       float val = v[0];
 #pragma unroll
@@ -278,8 +227,8 @@ __global__ __launch_bounds__(64 * FS_GRAD_ROWS) void fsum_grad_kernel(tt2_forwar
   const int b = blockIdx.x / (unsigned)blocks;
   const int n = (blockIdx.x % (unsigned)blocks) * FS_GRAD_ROWS + w;
   if (n >= a.tq) return;   // wave-uniform
-  const int Ty = fs_len(a.tq, a.q_len, b);
-  const int Tx = fs_len(a.tk, a.key_len, b);
+  const int Ty = len_limit(a.tq, a.q_len, b);
+  const int Tx = len_limit(a.tk, a.key_len, b);
   const int Te = min(Tx, Ty);
   float* d = a.dscores ? a.dscores + (int64_t)b * a.d_bs + (int64_t)n * a.d_ld : nullptr;
   float* gm = a.gamma ? a.gamma + (int64_t)b * a.g_bs + (int64_t)n * a.g_ld : nullptr;
@@ -327,11 +276,11 @@ __global__ __launch_bounds__(64 * FS_GRAD_ROWS) void fsum_grad_kernel(tt2_forwar
   }
 }
 
-// align_mono_kernel with the score block copied from memory (attention_mono.hip explains the walker's
-// ballots and the backtrack's windows)
+// The best path over the raw scores: align_mono_kernel's search (attention_mono.hip) with the score
+// block copied from memory and ls in place of ln P
 template <int KC>
-__global__ __launch_bounds__(FS_NT) void fsum_path_kernel(tt2_forward_sum_args a) {
-  using C = FsCfg<KC>;
+__global__ __launch_bounds__(WALK_NT) void fsum_path_kernel(tt2_forward_sum_args a) {
+  using C = WalkCfg<KC>;
   constexpr int R = C::R, NK = C::NK, SLD = C::SLD, SBUF = C::SBUF;
   __shared__ __attribute__((aligned(16))) char smem[2 * SBUF * 4 + C::MOVE_BYTES + KC * 4];
   float* sS = reinterpret_cast<float*>(smem);
@@ -343,38 +292,38 @@ __global__ __launch_bounds__(FS_NT) void fsum_path_kernel(tt2_forward_sum_args a
 
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const int b = blockIdx.x;
-  const int Ty = fs_len(a.tq, a.q_len, b);
-  const int Tx = fs_len(a.tk, a.key_len, b);
+  const int Ty = len_limit(a.tq, a.q_len, b);
+  const int Tx = len_limit(a.tk, a.key_len, b);
   const int Te = min(Tx, Ty);
   int32_t* path = a.path + (int64_t)b * a.tq;
   int32_t* dur = a.durations + (int64_t)b * a.tk;
   if (Ty <= 0 || Tx <= 0) {   // block-uniform
-    for (int n = tid; n < a.tq; n += FS_NT) path[n] = -1;
-    for (int t = tid; t < a.tk; t += FS_NT) dur[t] = 0;
+    for (int n = tid; n < a.tq; n += WALK_NT) path[n] = -1;
+    for (int t = tid; t < a.tk; t += WALK_NT) dur[t] = 0;
     if (tid == 0) a.logp[b] = 0.f;
     return;
   }
   const float* sc = a.scores + (int64_t)b * a.s_bs;
-  const bool mv_lds = fs_move_in_lds(a.tq, a.tk);
+  const bool mv_lds = walk_move_in_lds(a.tq, a.tk);
   uint64_t* mvL = reinterpret_cast<uint64_t*>(smem + 2 * SBUF * 4);
   uint64_t* mvG = reinterpret_cast<uint64_t*>(a.workspace) + (int64_t)b * a.tq * R;
-  const int nblk = (Ty + FS_RB - 1) / FS_RB;
+  const int nblk = (Ty + WALK_RB - 1) / WALK_RB;
 
-  for (int t = tid; t < KC; t += FS_NT) hist[t] = 0;
+  for (int t = tid; t < KC; t += WALK_NT) hist[t] = 0;
 
   auto produce = [&](int i) {
     float* S = sS + (i & 1) * SBUF;
-    constexpr int PR = FS_RB / FS_NP;   // rows per producer wave, their loads issued together
+    constexpr int PR = WALK_RB / WALK_NP;   // rows per producer wave, their loads issued together
     float x[PR][NK];
 #pragma unroll
     for (int q = 0; q < PR; ++q) {
-      const int n = FS_RB * i + w + FS_NP * q;
+      const int n = WALK_RB * i + w + WALK_NP * q;
       if (n < Ty) fs_row_load<NK>(sc + (int64_t)n * a.s_ld, Te, lane, x[q]);
     }
 #pragma unroll
     for (int q = 0; q < PR; ++q) {
-      const int r = w + FS_NP * q;
-      if (FS_RB * i + r >= Ty) break;
+      const int r = w + WALK_NP * q;
+      if (WALK_RB * i + r >= Ty) break;
 #pragma unroll
       for (int k = 0; k < NK; ++k) S[r * SLD + lane + 64 * k] = x[q][k];
     }
@@ -385,48 +334,11 @@ __global__ __launch_bounds__(FS_NT) void fsum_path_kernel(tt2_forward_sum_args a
   for (int j = 0; j < R; ++j) v[j] = -INFINITY;
   auto consume = [&](int i, auto LDSC) {   // LDSC: the move words go to LDS (else to the workspace)
     const float* S = sS + (i & 1) * SBUF + lane * R;
-    const int n0 = FS_RB * i, n1 = min(n0 + FS_RB, Ty);
-    auto row = [&](const float (&s)[R], int n) {
-      const float below = __int_as_float(__builtin_amdgcn_update_dpp(
-          __float_as_int(-INFINITY), __float_as_int(v[R - 1]), 0x138, 0xF, 0xF, false));
-      uint64_t bal[R];
-#pragma unroll
-      for (int j = R - 1; j >= 0; --j) {
-        const float prev = j ? v[j - 1] : below;
-        const bool m = prev > v[j];              // strict: a tie stays on the key
-        bal[j] = __ballot(m);
-        v[j] = s[j] + (m ? prev : v[j]);
-      }
-      if (lane == 0) {
-        if constexpr (decltype(LDSC)::value) {
-#pragma unroll
-          for (int j = 0; j < R; ++j) mvL[n * R + j] = bal[j];
-        } else {
-#pragma unroll
-          for (int j = 0; j < R; ++j) mvG[(int64_t)n * R + j] = bal[j];
-        }
-      }
-    };
-    float sa[R], sb[R];
-    fs_ld_row<R>(sa, S);
-    int n = n0;
-    if (i == 0) {   // row 0: only key 0 can be reached
-#pragma unroll
-      for (int j = 0; j < R; ++j) v[j] = (lane == 0 && j == 0) ? sa[0] : -INFINITY;
-      fs_ld_row<R>(sa, S + SLD);
-      n = 1;
-    }
-    for (; n + 1 < n1; n += 2) {
-      fs_ld_row<R>(sb, S + (n + 1 - n0) * SLD);
-      row(sa, n);
-      fs_ld_row<R>(sa, S + (n + 2 - n0) * SLD);
-      row(sb, n + 1);
-    }
-    if (n < n1) row(sa, n);
+    walk_block<R, SLD, decltype(LDSC)::value>(v, S, i, Ty, lane, mvL, mvG);
   };
 
   for (int i = 0; i <= nblk; ++i) {
-    if (w < FS_NP) {
+    if (w < WALK_NP) {
       if (i < nblk) produce(i);
     } else if (i > 0) {
       if (mv_lds) consume(i - 1, std::true_type{});
@@ -436,7 +348,7 @@ __global__ __launch_bounds__(FS_NT) void fsum_path_kernel(tt2_forward_sum_args a
   }
 
   // ---- backtrack (the walker wave, which wrote the bits), CH frames at a time
-  if (w == FS_NP) {
+  if (w == WALK_NP) {
     constexpr int CH = 64 - R;
     int t = __builtin_amdgcn_readfirstlane(Te - 1);
     for (int nb = Ty - 1; nb >= 0; nb -= CH) {
@@ -481,13 +393,13 @@ __global__ __launch_bounds__(FS_NT) void fsum_path_kernel(tt2_forward_sum_args a
     }
   }
   __syncthreads();
-  for (int n = Ty + tid; n < a.tq; n += FS_NT) path[n] = -1;
-  for (int t = tid; t < a.tk; t += FS_NT) dur[t] = hist[t];
+  for (int n = Ty + tid; n < a.tq; n += WALK_NT) path[n] = -1;
+  for (int t = tid; t < a.tk; t += WALK_NT) dur[t] = hist[t];
 
   // ---- ls along the path: a wave per row forms the row's log-sum-exp as the forward does, LB rows'
   // loads issued together
   constexpr int LB = 4;
-  for (int n0 = w * LB; n0 < Ty; n0 += (FS_NP + 1) * LB) {
+  for (int n0 = w * LB; n0 < Ty; n0 += (WALK_NP + 1) * LB) {
     float x[LB][NK], sp[LB];
 #pragma unroll
     for (int q = 0; q < LB; ++q) {
@@ -516,54 +428,43 @@ __global__ __launch_bounds__(FS_NT) void fsum_path_kernel(tt2_forward_sum_args a
   }
 }
 
-int fs_err(const char* who, const char* msg) {
-  return tt2_set_error(TT2_E_INVALID, (std::string(who) + ": " + msg).c_str());
-}
-
 // What the three entries refuse alike
 int fs_check(const char* who, const tt2_forward_sum_args* p) {
-  if (!p) return fs_err(who, "args required");
-  if (p->batch < 0 || p->tq < 0 || p->tk < 0) return fs_err(who, "negative batch / tq / tk");
-  if (p->tk > TT2_FSUM_MAX_KEYS) return fs_err(who, "tk above TT2_FSUM_MAX_KEYS");
-  if (p->tq > TT2_FSUM_MAX_FRAMES) return fs_err(who, "tq above TT2_FSUM_MAX_FRAMES");
-  if (p->s_ld < p->tk) return fs_err(who, "s_ld < tk");
-  return TT2_OK;
-}
-
-int fs_workspace(const char* who, const tt2_forward_sum_args* p, size_t need, uintptr_t align) {
-  if (need && (!p->workspace || p->workspace_bytes < need || (reinterpret_cast<uintptr_t>(p->workspace) & (align - 1))))
-    return fs_err(who, ("workspace too small or misaligned: " + std::to_string(need) + " bytes needed").c_str());
+  if (!p) return tt2_invalid(who, "args required");
+  if (p->batch < 0 || p->tq < 0 || p->tk < 0) return tt2_invalid(who, "negative batch / tq / tk");
+  if (p->tk > TT2_FSUM_MAX_KEYS) return tt2_invalid(who, "tk above TT2_FSUM_MAX_KEYS");
+  if (p->tq > TT2_FSUM_MAX_FRAMES) return tt2_invalid(who, "tq above TT2_FSUM_MAX_FRAMES");
+  if (p->s_ld < p->tk) return tt2_invalid(who, "s_ld < tk");
   return TT2_OK;
 }
 
 template <int DIR> void fs_walk_launch(const tt2_forward_sum_args& a, hipStream_t s) {
-  const int kc = fs_kc(a.tk);
-  if (kc == 128) hipLaunchKernelGGL((fsum_walk_kernel<128, DIR>), dim3(a.batch), dim3(FS_NT), 0, s, a);
-  else if (kc == 256) hipLaunchKernelGGL((fsum_walk_kernel<256, DIR>), dim3(a.batch), dim3(FS_NT), 0, s, a);
-  else hipLaunchKernelGGL((fsum_walk_kernel<512, DIR>), dim3(a.batch), dim3(FS_NT), 0, s, a);
+  walk_by_kc(a.tk, [&](auto kc) {
+    hipLaunchKernelGGL((fsum_walk_kernel<decltype(kc)::value, DIR>), dim3(a.batch), dim3(WALK_NT), 0, s, a);
+  });
 }
 
 }  // namespace
 
 extern "C" size_t tt2_forward_sum_bwd_workspace_size(int batch, int tq, int tk) {
   if (batch <= 0 || tq <= 0 || tk <= 0 || tk > TT2_FSUM_MAX_KEYS) return 0;
-  return (size_t)batch * tq * fs_kc(tk) * sizeof(float);
+  return (size_t)batch * tq * walk_kc(tk) * sizeof(float);
 }
 
 extern "C" size_t tt2_forward_sum_path_workspace_size(int batch, int tq, int tk) {
-  if (batch <= 0 || tq <= 0 || tk <= 0 || tk > TT2_FSUM_MAX_KEYS || fs_move_in_lds(tq, tk)) return 0;
-  return (size_t)batch * fs_move_bytes(tq, tk);
+  if (batch <= 0 || tq <= 0 || tk <= 0 || tk > TT2_FSUM_MAX_KEYS || walk_move_in_lds(tq, tk)) return 0;
+  return (size_t)batch * walk_move_bytes(tq, tk);
 }
 
 extern "C" int tt2_forward_sum_fwd(const tt2_forward_sum_args* p, hipStream_t s) {
   const char* who = "tt2_forward_sum_fwd";
   const int rc = fs_check(who, p);
   if (rc != TT2_OK) return rc;
-  if (p->alpha && p->a_ld < p->tk) return fs_err(who, "a_ld < tk");
+  if (p->alpha && p->a_ld < p->tk) return tt2_invalid(who, "a_ld < tk");
   if (p->batch == 0) return TT2_OK;
-  if (!p->loss) return fs_err(who, "loss required");
-  if (p->tq > 0 && !p->lse) return fs_err(who, "lse required");
-  if (p->tq > 0 && p->tk > 0 && !p->scores) return fs_err(who, "scores required");
+  if (!p->loss) return tt2_invalid(who, "loss required");
+  if (p->tq > 0 && !p->lse) return tt2_invalid(who, "lse required");
+  if (p->tq > 0 && p->tk > 0 && !p->scores) return tt2_invalid(who, "scores required");
   fs_walk_launch<0>(*p, s);
   return tt2_check_launch(hipGetLastError(), who);
 }
@@ -572,21 +473,22 @@ extern "C" int tt2_forward_sum_bwd(const tt2_forward_sum_args* p, hipStream_t s)
   const char* who = "tt2_forward_sum_bwd";
   int rc = fs_check(who, p);
   if (rc != TT2_OK) return rc;
-  if (p->a_ld < p->tk) return fs_err(who, "a_ld < tk");
-  if (p->dscores && p->d_ld < p->tk) return fs_err(who, "d_ld < tk");
-  if (p->gamma && p->g_ld < p->tk) return fs_err(who, "g_ld < tk");
+  if (p->a_ld < p->tk) return tt2_invalid(who, "a_ld < tk");
+  if (p->dscores && p->d_ld < p->tk) return tt2_invalid(who, "d_ld < tk");
+  if (p->gamma && p->g_ld < p->tk) return tt2_invalid(who, "g_ld < tk");
   const int blocks = (p->tq + FS_GRAD_ROWS - 1) / FS_GRAD_ROWS;
-  if ((int64_t)p->batch * blocks > INT_MAX) return fs_err(who, "more than 2^31 - 1 work groups");
-  rc = fs_workspace(who, p, tt2_forward_sum_bwd_workspace_size(p->batch, p->tq, p->tk), 16);
+  if ((int64_t)p->batch * blocks > INT_MAX) return tt2_invalid(who, "more than 2^31 - 1 work groups");
+  rc = tt2_need_workspace(who, p->workspace, p->workspace_bytes,
+                          tt2_forward_sum_bwd_workspace_size(p->batch, p->tq, p->tk), 16);
   if (rc != TT2_OK) return rc;
   if (p->batch == 0 || p->tq == 0 || p->tk == 0) return TT2_OK;
-  if (!p->dscores && !p->gamma) return fs_err(who, "dscores or gamma required");
-  if (!p->scores || !p->lse || !p->alpha) return fs_err(who, "scores, lse and alpha required");
+  if (!p->dscores && !p->gamma) return tt2_invalid(who, "dscores or gamma required");
+  if (!p->scores || !p->lse || !p->alpha) return tt2_invalid(who, "scores, lse and alpha required");
   fs_walk_launch<1>(*p, s);
   rc = tt2_check_launch(hipGetLastError(), who);
   if (rc != TT2_OK) return rc;
   hipLaunchKernelGGL(fsum_grad_kernel, dim3((unsigned)(p->batch * blocks)), dim3(64 * FS_GRAD_ROWS), 0, s, *p,
-                     fs_kc(p->tk), blocks);
+                     walk_kc(p->tk), blocks);
   return tt2_check_launch(hipGetLastError(), who);
 }
 
@@ -594,15 +496,15 @@ extern "C" int tt2_forward_sum_path(const tt2_forward_sum_args* p, hipStream_t s
   const char* who = "tt2_forward_sum_path";
   int rc = fs_check(who, p);
   if (rc != TT2_OK) return rc;
-  rc = fs_workspace(who, p, tt2_forward_sum_path_workspace_size(p->batch, p->tq, p->tk), 8);
+  rc = tt2_need_workspace(who, p->workspace, p->workspace_bytes,
+                          tt2_forward_sum_path_workspace_size(p->batch, p->tq, p->tk), 8);
   if (rc != TT2_OK) return rc;
   if (p->batch == 0) return TT2_OK;
   if (!p->logp || (p->tq > 0 && !p->path) || (p->tk > 0 && !p->durations))
-    return fs_err(who, "path, durations and logp required");
-  if (p->tq > 0 && p->tk > 0 && !p->scores) return fs_err(who, "scores required");
-  const int kc = fs_kc(p->tk);
-  if (kc == 128) hipLaunchKernelGGL(fsum_path_kernel<128>, dim3(p->batch), dim3(FS_NT), 0, s, *p);
-  else if (kc == 256) hipLaunchKernelGGL(fsum_path_kernel<256>, dim3(p->batch), dim3(FS_NT), 0, s, *p);
-  else hipLaunchKernelGGL(fsum_path_kernel<512>, dim3(p->batch), dim3(FS_NT), 0, s, *p);
+    return tt2_invalid(who, "path, durations and logp required");
+  if (p->tq > 0 && p->tk > 0 && !p->scores) return tt2_invalid(who, "scores required");
+  walk_by_kc(p->tk, [&](auto kc) {
+    hipLaunchKernelGGL(fsum_path_kernel<decltype(kc)::value>, dim3(p->batch), dim3(WALK_NT), 0, s, *p);
+  });
   return tt2_check_launch(hipGetLastError(), who);
 }

@@ -26,7 +26,6 @@
 
 #include <algorithm>
 #include <cmath>
-#include <string>
 
 #include "tt2_capi.h"
 #include "tt2_internal.h"
@@ -394,7 +393,7 @@ __global__ __launch_bounds__(LK_THREADS) void loud_apply(tt2_loudness_args a, lk
   }
 }
 
-int lk_err(const char* msg) { return tt2_set_error(TT2_E_INVALID, (std::string("tt2_loudness: ") + msg).c_str()); }
+int lk_err(const char* msg) { return tt2_invalid("tt2_loudness", msg); }
 
 size_t lk_up16(size_t n) { return (n + 15) & ~(size_t)15; }
 

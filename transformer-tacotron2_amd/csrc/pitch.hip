@@ -3,7 +3,6 @@
 #include <limits.h>
 #include <math.h>
 
-#include <string>
 
 #include "tt2_capi.h"
 #include "tt2_internal.h"
@@ -200,7 +199,7 @@ __global__ __launch_bounds__(64 * YIN_NW) void yin_kernel(tt2_yin_args a, int gr
   }
 }
 
-int yin_err(const char* msg) { return tt2_set_error(TT2_E_INVALID, (std::string("tt2_yin: ") + msg).c_str()); }
+int yin_err(const char* msg) { return tt2_invalid("tt2_yin", msg); }
 }  // namespace
 
 extern "C" int tt2_yin(const tt2_yin_args* p, hipStream_t s) {

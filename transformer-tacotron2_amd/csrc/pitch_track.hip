@@ -2,7 +2,6 @@
 // definition.  A translation unit of its own: no other kernel's code depends on it.
 #include <math.h>
 
-#include <string>
 
 #include "tt2_capi.h"
 #include "tt2_internal.h"
@@ -213,7 +212,7 @@ __global__ __launch_bounds__(PT_NT) void pitch_track_kernel(tt2_pitch_track_args
   }
 }
 
-int pt_err(const char* msg) { return tt2_set_error(TT2_E_INVALID, (std::string("tt2_pitch_track: ") + msg).c_str()); }
+int pt_err(const char* msg) { return tt2_invalid("tt2_pitch_track", msg); }
 bool pt_cost_ok(float x) { return isfinite(x) && x >= 0.f; }
 }  // namespace
 
@@ -239,9 +238,10 @@ extern "C" int tt2_pitch_track(const tt2_pitch_track_args* p, hipStream_t s) {
     return tt2_check_launch(e, "tt2_pitch_track");
   }
   if (!p->cmnd) return pt_err("cmnd required");
-  const size_t need = tt2_pitch_track_workspace_size(p->batch, p->t, p->tau_min, p->tau_max);
-  if (!p->workspace || p->workspace_bytes < need || (reinterpret_cast<uintptr_t>(p->workspace) & 3))
-    return pt_err(("workspace too small or misaligned: " + std::to_string(need) + " bytes needed").c_str());
+  // (batch, t >= 1 and the lags hold here: the size is never 0)
+  const int rc = tt2_need_workspace("tt2_pitch_track", p->workspace, p->workspace_bytes,
+                                    tt2_pitch_track_workspace_size(p->batch, p->t, p->tau_min, p->tau_max), 4);
+  if (rc != TT2_OK) return rc;
   const int S = p->tau_max - p->tau_min + 1;
   const dim3 grid((unsigned)p->batch), block(PT_NT);
   if (S <= 128) hipLaunchKernelGGL(pitch_track_kernel<2>, grid, block, 0, s, *p);

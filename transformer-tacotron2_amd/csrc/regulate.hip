@@ -16,7 +16,6 @@
 #include <limits.h>
 
 #include <algorithm>
-#include <string>
 
 #include "tt2_capi.h"
 #include "tt2_internal.h"
@@ -194,10 +193,6 @@ __global__ __launch_bounds__(RG_THREADS) void regulate_bwd_kernel(tt2_regulate_a
   }
 }
 
-int rg_err(const char* who, const char* msg) {
-  return tt2_set_error(TT2_E_INVALID, (std::string(who) + ": " + msg).c_str());
-}
-
 // 16-byte units need both bases on 16 bytes and every stride and dim a whole number of units
 bool rg_chunks_ok(const tt2_regulate_args& p, int n) {
   const uintptr_t bases = reinterpret_cast<uintptr_t>(p.src) | reinterpret_cast<uintptr_t>(p.dst);
@@ -207,12 +202,12 @@ bool rg_chunks_ok(const tt2_regulate_args& p, int n) {
 
 // What fwd and bwd refuse alike; map_cols is the extent of a row of `map`
 int rg_check(const char* who, const tt2_regulate_args* p, int64_t map_cols) {
-  if (!p) return rg_err(who, "args required");
-  if (p->batch < 0 || p->tx < 0 || p->n_out < 0 || p->dim < 0) return rg_err(who, "negative batch / tx / n_out / dim");
-  if (p->tx > TT2_REGULATE_MAX_PHONEMES) return rg_err(who, "tx above TT2_REGULATE_MAX_PHONEMES");
-  if (p->dtype != TT2_DT_F32 && p->dtype != TT2_DT_BF16) return rg_err(who, "dtype must be TT2_DT_F32 or TT2_DT_BF16");
-  if (p->src_ld < p->dim || p->dst_ld < p->dim) return rg_err(who, "src_ld or dst_ld < dim");
-  if (p->map_ld < map_cols) return rg_err(who, "map_ld below the extent of a row of map");
+  if (!p) return tt2_invalid(who, "args required");
+  if (p->batch < 0 || p->tx < 0 || p->n_out < 0 || p->dim < 0) return tt2_invalid(who, "negative batch / tx / n_out / dim");
+  if (p->tx > TT2_REGULATE_MAX_PHONEMES) return tt2_invalid(who, "tx above TT2_REGULATE_MAX_PHONEMES");
+  if (p->dtype != TT2_DT_F32 && p->dtype != TT2_DT_BF16) return tt2_invalid(who, "dtype must be TT2_DT_F32 or TT2_DT_BF16");
+  if (p->src_ld < p->dim || p->dst_ld < p->dim) return tt2_invalid(who, "src_ld or dst_ld < dim");
+  if (p->map_ld < map_cols) return tt2_invalid(who, "map_ld below the extent of a row of map");
   return TT2_OK;
 }
 
@@ -220,15 +215,15 @@ int rg_check(const char* who, const tt2_regulate_args* p, int64_t map_cols) {
 
 extern "C" int tt2_regulate_plan(const tt2_regulate_plan_args* p, hipStream_t s) {
   const char* who = "tt2_regulate_plan";
-  if (!p) return rg_err(who, "args required");
-  if (p->batch < 0 || p->tx < 0 || p->n_out < 0) return rg_err(who, "negative batch / tx / n_out");
-  if (p->tx > TT2_REGULATE_MAX_PHONEMES) return rg_err(who, "tx above TT2_REGULATE_MAX_PHONEMES");
-  if (p->dur_ld < p->tx || p->ends_ld < p->tx) return rg_err(who, "dur_ld or ends_ld < tx");
-  if (p->index && p->index_ld < p->n_out) return rg_err(who, "index_ld < n_out");
+  if (!p) return tt2_invalid(who, "args required");
+  if (p->batch < 0 || p->tx < 0 || p->n_out < 0) return tt2_invalid(who, "negative batch / tx / n_out");
+  if (p->tx > TT2_REGULATE_MAX_PHONEMES) return tt2_invalid(who, "tx above TT2_REGULATE_MAX_PHONEMES");
+  if (p->dur_ld < p->tx || p->ends_ld < p->tx) return tt2_invalid(who, "dur_ld or ends_ld < tx");
+  if (p->index && p->index_ld < p->n_out) return tt2_invalid(who, "index_ld < n_out");
   const int slices = p->index ? (int)std::max<int64_t>(1, std::min<int64_t>(RG_PLAN_SLICES, ((int64_t)p->n_out + RG_PLAN_SLICE_ROWS - 1) / RG_PLAN_SLICE_ROWS)) : 1;
-  if ((int64_t)p->batch * slices > INT_MAX) return rg_err(who, "more than 2^31 - 1 work groups");
+  if ((int64_t)p->batch * slices > INT_MAX) return tt2_invalid(who, "more than 2^31 - 1 work groups");
   if (p->batch == 0) return TT2_OK;
-  if (p->tx > 0 && (!p->durations || !p->ends)) return rg_err(who, "durations and ends required");
+  if (p->tx > 0 && (!p->durations || !p->ends)) return tt2_invalid(who, "durations and ends required");
   if (p->tx == 0 && !p->frames && !p->total && !(p->index && p->n_out > 0)) return TT2_OK;   // nothing to write
   hipLaunchKernelGGL(regulate_plan_kernel, dim3((unsigned)(p->batch * slices)), dim3(RG_THREADS), 0, s, *p, slices);
   return tt2_check_launch(hipGetLastError(), who);
@@ -241,10 +236,10 @@ extern "C" int tt2_regulate_fwd(const tt2_regulate_args* p, hipStream_t s) {
   const int n = p->dtype == TT2_DT_F32 ? 4 : 8;
   const bool chunks = rg_chunks_ok(*p, n);
   const rg_geom g = rg_geometry(p->dim, chunks ? n : 1, p->n_out, FW_ROWS);
-  if ((int64_t)p->batch * g.blocks > INT_MAX) return rg_err(who, "more than 2^31 - 1 work groups");
+  if ((int64_t)p->batch * g.blocks > INT_MAX) return tt2_invalid(who, "more than 2^31 - 1 work groups");
   if (p->batch == 0 || p->n_out == 0 || p->dim == 0) return TT2_OK;
-  if (!p->dst) return rg_err(who, "dst required");
-  if (p->tx > 0 && (!p->src || !p->map)) return rg_err(who, "src and map required");
+  if (!p->dst) return tt2_invalid(who, "dst required");
+  if (p->tx > 0 && (!p->src || !p->map)) return tt2_invalid(who, "src and map required");
   const dim3 grid((unsigned)(p->batch * g.blocks)), block(RG_THREADS);
   if (chunks) {
     hipLaunchKernelGGL(regulate_fwd_kernel<u32x4>, grid, block, 0, s, *p, g);
@@ -263,10 +258,10 @@ extern "C" int tt2_regulate_bwd(const tt2_regulate_args* p, hipStream_t s) {
   const int n = p->dtype == TT2_DT_F32 ? 4 : 8;
   const bool chunks = rg_chunks_ok(*p, n);
   const rg_geom g = rg_geometry(p->dim, chunks ? n : 1, p->tx, 1);
-  if ((int64_t)p->batch * g.blocks > INT_MAX) return rg_err(who, "more than 2^31 - 1 work groups");
+  if ((int64_t)p->batch * g.blocks > INT_MAX) return tt2_invalid(who, "more than 2^31 - 1 work groups");
   if (p->batch == 0 || p->tx == 0 || p->dim == 0) return TT2_OK;
-  if (!p->dst) return rg_err(who, "dst required");
-  if (p->n_out > 0 && (!p->src || !p->map)) return rg_err(who, "src and map required");
+  if (!p->dst) return tt2_invalid(who, "dst required");
+  if (p->n_out > 0 && (!p->src || !p->map)) return tt2_invalid(who, "src and map required");
   const dim3 grid((unsigned)(p->batch * g.blocks)), block(RG_THREADS);
   if (p->dtype == TT2_DT_F32) {
     if (chunks) hipLaunchKernelGGL((regulate_bwd_kernel<float, 4>), grid, block, 0, s, *p, g);

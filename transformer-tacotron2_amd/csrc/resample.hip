@@ -3,7 +3,6 @@
 #include <limits.h>
 
 #include <algorithm>
-#include <string>
 
 #include "tt2_capi.h"
 #include "tt2_internal.h"
@@ -169,7 +168,7 @@ __global__ __launch_bounds__(RS_THREADS) void resample_kernel(tt2_resample_args 
   }
 }
 
-int rs_err(const char* msg) { return tt2_set_error(TT2_E_INVALID, (std::string("tt2_resample: ") + msg).c_str()); }
+int rs_err(const char* msg) { return tt2_invalid("tt2_resample", msg); }
 
 // The tiling of one call; false when it needs more than INT_MAX work groups.
 bool rs_make_plan(const tt2_resample_args* p, rs_plan* pl, int64_t* groups) {

@@ -29,6 +29,16 @@ extern "C" int tt2_check_launch(hipError_t err, const char* what) {
   return TT2_E_LAUNCH;
 }
 
+int tt2_invalid(const char* who, const char* msg) {
+  g_err = std::string(who) + ": " + msg;
+  return TT2_E_INVALID;
+}
+
+int tt2_need_workspace(const char* who, const void* ws, size_t have, size_t need, size_t align) {
+  if (!need || (ws && have >= need && !(reinterpret_cast<uintptr_t>(ws) & (align - 1)))) return TT2_OK;
+  return tt2_invalid(who, ("workspace too small or misaligned: " + std::to_string(need) + " bytes needed").c_str());
+}
+
 int tt2_cu_count() {
   static int cache[64] = {0};
   int dev = 0;

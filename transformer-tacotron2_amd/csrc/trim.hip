@@ -14,7 +14,6 @@
 
 #include <algorithm>
 #include <cmath>
-#include <string>
 
 #include "tt2_capi.h"
 #include "tt2_internal.h"
@@ -183,7 +182,7 @@ __global__ __launch_bounds__(TR_THREADS) void trim_copy(tt2_trim_args a, tr_plan
   }
 }
 
-int tr_err(const char* msg) { return tt2_set_error(TT2_E_INVALID, (std::string("tt2_trim: ") + msg).c_str()); }
+int tr_err(const char* msg) { return tt2_invalid("tt2_trim", msg); }
 
 size_t tr_meta_bytes(int64_t batch) { return ((size_t)batch * 2 * sizeof(int32_t) + 15) & ~(size_t)15; }
 }  // namespace

@@ -280,6 +280,14 @@ TT2_DEV float act_grad_from_out(int act, float z) {
   return act == ACT_RELU ? (z > 0.f ? 1.f : 0.f) : (act == ACT_TANH ? 1.f - z * z : 1.f);
 }
 
+// rows of batch element b that count: T, cut to the per-batch length (NULL: none), never negative
+TT2_DEV int len_limit(int T, const int32_t* len, int b) {
+  int l = T;
+  if (len) l = min(l, len[b]);
+  return l < 0 ? 0 : l;
+}
+constexpr float LN2 = 0.6931471805599453f;
+
 // ---------------------------------------------------------------- host side of a launch
 // work groups of a grid-stride kernel over `total` items, `per` to a work group: 1 .. cap
 inline int grid_for(int64_t total, int per = 256, int cap = 8192) {

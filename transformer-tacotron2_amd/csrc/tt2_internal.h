@@ -6,6 +6,13 @@ extern "C" {
 int tt2_set_error(int code, const char* msg);
 int tt2_check_launch(hipError_t err, const char* what);
 }
+// What every entry point refuses with (runtime.cpp; hidden: not part of the library's exports).
+// tt2_invalid: sets "who: msg" and returns TT2_E_INVALID.  tt2_need_workspace: TT2_OK when need
+// is 0 or `ws` holds `have` >= need bytes at a multiple of `align` (a power of two), else
+// tt2_invalid(who, "workspace too small or misaligned: <need> bytes needed").
+__attribute__((visibility("hidden"))) int tt2_invalid(const char* who, const char* msg);
+__attribute__((visibility("hidden"))) int tt2_need_workspace(const char* who, const void* ws, size_t have, size_t need,
+                                                             size_t align);
 // compute units of the current device (cached per device; 256 on an MI355X)
 int tt2_cu_count();
 // reduce.hip: launches the one reduce_rows_kernel, dst[c] = beta * dst[c] + sum_r src[r * ld + c],
