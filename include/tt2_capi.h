@@ -822,6 +822,90 @@ int tt2_forward_sum_fwd(const tt2_forward_sum_args* a, hipStream_t stream);
 int tt2_forward_sum_bwd(const tt2_forward_sum_args* a, hipStream_t stream);
 int tt2_forward_sum_path(const tt2_forward_sum_args* a, hipStream_t stream);
 
+/* ---------------------------------------------------------- Gaussian upsampling
+ * The soft length regulator (Non-Attentive Tacotron, Parallel Tacotron; ESPnet's GaussianUpsampling
+ * in JETS and VITS): phoneme states to frame states through softmax weights that are a function of
+ * two per-phoneme vectors and the frame index, and the gradient with respect to the states and to
+ * both vectors (and to an optional bias).  An attention whose scores are analytic: the
+ * [frames, phonemes] weight matrix is never written, forward or backward.  No host synchronisation,
+ * no floating-point atomics, every reduction order fixed: all outputs are bit-identical run to run.
+ *   Lengths.  For utterance b, Tx_b = clamp(key_len[b], 0, tx) and Ty_b = clamp(q_len[b], 0, n_out);
+ * both are device vectors and NULL means tx / n_out.
+ *   Per-phoneme inputs.  center, prec and (optional) bias are f32 [batch, p_ld] with finite values
+ * and prec >= 0; entries at t >= Tx_b are never read.
+ *   Frame position.  x_n = n + offset, with offset a float argument.
+ *     e[n][t] = bias[t] - prec[t] * (x_n - center[t])^2         t < Tx_b   (bias NULL: 0)
+ *     W[n][.] = softmax over t < Tx_b of e[n][.]                 (row maximum subtracted)
+ *     y[n][c] = sum_{t < Tx_b} W[n][t] * h[t][c]                 n < Ty_b, c < dim
+ *     lse[n]  = ln sum_t exp e[n][t]                             n < Ty_b
+ * y is accumulated in f32 and rounded once to the output dtype.  y and lse are exactly +0 for
+ * Ty_b <= n < n_out and when Tx_b = 0; nothing is written at or past column dim or row n_out; rows
+ * of h at t >= Tx_b are never read.  ESPnet's convention is prec = delta, bias NULL, offset = 0;
+ * Non-Attentive Tacotron's is prec = 1 / (2 sigma^2), bias = -ln sigma, offset = 1.
+ *   tt2_gauss_upsample_fwd writes y and lse in one launch (online softmax over phoneme tiles).  With
+ * a bf16 dtype the weights of a tile enter the matrix product rounded to bf16 (relative to the
+ * running row maximum), the products are exact and the accumulation is f32; with f32 every product is
+ * an f32 product.
+ *   tt2_gauss_upsample_bwd reads h, center, prec, bias, dy, and the y and lse the forward left.  With
+ * delta[n] = sum_c dy[n][c] y[n][c], dW[n][t] = sum_c dy[n][c] h[t][c] and dE = W o (dW - delta),
+ * all sums over n < Ty_b:
+ *     dh[t][c]   =  sum_n W[n][t] dy[n][c]
+ *     dbias[t]   =  sum_n dE[n][t]
+ *     dcenter[t] =  sum_n dE[n][t] * 2 prec[t] (x_n - center[t])
+ *     dprec[t]   = -sum_n dE[n][t] (x_n - center[t])^2
+ * W is recomputed as exp(e - lse).  Each of the four outputs is optional (NULL), at least one must be
+ * asked for, and each is the same bit for bit whichever others are asked for.  Each is written for
+ * every t < tx and is exactly +0 at t >= Tx_b; rows of dy and y at n >= Ty_b are never read.  dbias
+ * may be asked for with bias NULL.  A work group owns 32 phonemes and walks frames in ascending order;
+ * an utterance of more than 128 frames is shared among up to 16 work groups per phoneme tile, whose
+ * f32 partials go through `workspace` and are added in ascending order of their frames by a last
+ * launch (the split is a function of n_out alone).  delta goes through `workspace` too: 16-B aligned,
+ * tt2_gauss_upsample_bwd_workspace_size bytes: 0 when batch, tx or n_out is 0, else 4 batch n_out for
+ * delta plus, with s > 1 work groups per phoneme tile, 4 s batch tx (dim + 3) for the partials (each
+ * part rounded up to 16 bytes).
+ *   Types and layout.  h, y, dy and dh share one dtype, TT2_DT_F32 or TT2_DT_BF16.  Element (b, r, c)
+ * of each is at base + b * bs + r * ld + c in elements, so column slices of wider buffers go in as
+ * they are; any dim and any element alignment work, rows moving into LDS in 16-byte chunks where the
+ * base sits on 16 bytes and ld, bs and dim are whole numbers of chunks, element by element otherwise,
+ * with the same result.  center, prec, bias and their gradients share the row stride p_ld; lse is
+ * [batch, lse_ld].  Everything per phoneme or per frame is f32.
+ *   Contract.  Inputs are finite.  NaN or +-inf inside one utterance may make that utterance's
+ * outputs NaN; every other utterance's outputs stay bit-identical.
+ *   Limits: tx <= TT2_REGULATE_MAX_PHONEMES, dim <= TT2_UPSAMPLE_MAX_DIM.
+ *   Refused with TT2_E_INVALID before any launch, with a message that starts with the entry's name:
+ * null args; batch, tx, n_out or dim negative; tx or dim over the limits; a dtype other than f32 /
+ * bf16; h_ld < dim, y_ld < dim, p_ld < tx, lse_ld < n_out; dy_ld < dim, dh given with dh_ld < dim
+ * (bwd); an offset that is negative or not finite; more than 2^31 - 1 work groups; a workspace that
+ * is too small or misaligned (bwd); then, where the call has something to do, a null pointer it
+ * would read or write: lse, y with dim > 0, and center, prec or (dim > 0) h with tx > 0 (fwd); all
+ * four outputs null, and with n_out > 0 center, prec, lse or (dim > 0) h, dy, y (bwd).
+ *   Zero sizes.  batch = 0 succeeds without a launch, in both.  fwd with n_out = 0 succeeds without a
+ * launch and with tx = 0 writes +0 to every row of y and lse (h, center and prec may be NULL).  bwd
+ * with tx = 0 succeeds without a launch and with n_out = 0 writes +0 to every output asked for (the
+ * inputs may be NULL). */
+#define TT2_UPSAMPLE_MAX_DIM 512
+typedef struct tt2_gauss_upsample_args {
+  const void* h;             /* [batch, tx, dim] */
+  const float* center;       /* [batch, p_ld] */
+  const float* prec;         /* [batch, p_ld] */
+  const float* bias;         /* optional [batch, p_ld] */
+  const int32_t* q_len; const int32_t* key_len;   /* [batch], device (NULL: n_out / tx) */
+  void* y;                   /* [batch, n_out, dim]: fwd writes, bwd reads */
+  float* lse;                /* [batch, lse_ld]: fwd writes, bwd reads */
+  const void* dy;            /* [batch, n_out, dim]: bwd reads */
+  void* dh;                  /* optional [batch, tx, dim]: bwd writes */
+  float* dcenter;            /* optional [batch, p_ld]: bwd writes */
+  float* dprec;              /* optional [batch, p_ld]: bwd writes */
+  float* dbias;              /* optional [batch, p_ld]: bwd writes */
+  void* workspace; size_t workspace_bytes;
+  int64_t h_ld, h_bs, y_ld, y_bs, dy_ld, dy_bs, dh_ld, dh_bs, p_ld, lse_ld;   /* in elements */
+  int32_t batch, tx, n_out, dim, dtype;
+  float offset;
+} tt2_gauss_upsample_args;
+size_t tt2_gauss_upsample_bwd_workspace_size(int batch, int tx, int n_out, int dim);
+int tt2_gauss_upsample_fwd(const tt2_gauss_upsample_args* a, hipStream_t stream);
+int tt2_gauss_upsample_bwd(const tt2_gauss_upsample_args* a, hipStream_t stream);
+
 /* ------------------------------------------------------------------ decode
  * One query row per batch element (the AR decode step):
  * out[b*o_ld + 64h ..] = softmax(scale q k^T) v over keys j < n_b of batch b,

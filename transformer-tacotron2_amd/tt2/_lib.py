@@ -396,6 +396,28 @@ SIGNATURES.update({
 })
 
 
+UPSAMPLE_MAX_DIM = 512   # TT2_UPSAMPLE_MAX_DIM: a work group's phoneme tile holds every column in LDS
+
+
+class GaussUpsampleArgs(C.Structure):
+    """tt2_gauss_upsample_args: Gaussian upsampling (the soft length regulator) and its four gradients."""
+    _fields_ = [
+        ("h", vp), ("center", vp), ("prec", vp), ("bias", vp), ("q_len", vp), ("key_len", vp),
+        ("y", vp), ("lse", vp), ("dy", vp), ("dh", vp), ("dcenter", vp), ("dprec", vp), ("dbias", vp),
+        ("workspace", vp), ("workspace_bytes", sz),
+        ("h_ld", i64), ("h_bs", i64), ("y_ld", i64), ("y_bs", i64), ("dy_ld", i64), ("dy_bs", i64),
+        ("dh_ld", i64), ("dh_bs", i64), ("p_ld", i64), ("lse_ld", i64),
+        ("batch", i32), ("tx", i32), ("n_out", i32), ("dim", i32), ("dtype", i32), ("offset", f32),
+    ]
+
+
+SIGNATURES.update({
+    "tt2_gauss_upsample_bwd_workspace_size": ([C.c_int, C.c_int, C.c_int, C.c_int], C.c_size_t),
+    "tt2_gauss_upsample_fwd": ([C.POINTER(GaussUpsampleArgs), vp], C.c_int),
+    "tt2_gauss_upsample_bwd": ([C.POINTER(GaussUpsampleArgs), vp], C.c_int),
+})
+
+
 class ReduceArgs(C.Structure):
     _fields_ = [("src", vp), ("dst", vp), ("ld", i64), ("rows", i32), ("cols", i32), ("beta", f32)]
 

@@ -1043,6 +1043,93 @@ def forward_sum_path(scores, path, durations, logp, q_len=None, key_len=None, wo
     return path, durations, logp
 
 
+def _gu_mat(who, name, t, B, rows, D, dtype, out=False):
+    """Check that t is [B, rows, D] of `dtype` with a contiguous last dim (any row and batch stride; an
+    output's rows and utterances must not overlap); returns (ld, bs) in elements."""
+    if t.dim() != 3 or t.dtype != dtype or tuple(t.shape) != (B, rows, D):
+        raise ValueError(f"{who}: {name} must be {dtype} [{B}, {rows}, {D}], got {t.dtype} {tuple(t.shape)}")
+    if D > 1 and t.stride(2) != 1:
+        raise ValueError(f"{who}: {name} needs a contiguous last dim")
+    ld = _ld(t)
+    bs = t.stride(0) if B > 1 else max(t.stride(0), 0)
+    if ld < D or (out and B > 1 and rows > 0 and bs < (rows - 1) * ld + D):
+        raise ValueError(f"{who}: {name}'s rows overlap (strides {t.stride()} for {tuple(t.shape)})")
+    return ld, bs
+
+
+def _gu_args(who, h, center, prec, bias, y, lse, q_len, key_len, offset, vectors=()):
+    """The part of tt2_gauss_upsample_args that forward and backward share.  vectors: further
+    (name, tensor | None) per-phoneme f32 [B, >= Tx] tensors (the gradients), which must share the row
+    stride of center."""
+    if h is None or y is None or h.dim() != 3 or y.dim() != 3 or h.dtype not in (torch.float32, torch.bfloat16):
+        raise ValueError(f"{who}: h and y must be f32 or bf16 [B, rows, D]")
+    B, tx, D = h.shape
+    n_out = y.shape[1]
+    if tx > _lib.REGULATE_MAX_PHONEMES:
+        raise ValueError(f"{who}: Tx = {tx} above TT2_REGULATE_MAX_PHONEMES = {_lib.REGULATE_MAX_PHONEMES}")
+    if D > _lib.UPSAMPLE_MAX_DIM:
+        raise ValueError(f"{who}: dim = {D} above TT2_UPSAMPLE_MAX_DIM = {_lib.UPSAMPLE_MAX_DIM}")
+    offset = float(offset)
+    if not (0.0 <= offset < float("inf")):
+        raise ValueError(f"{who}: offset must be finite and >= 0, got {offset}")
+    g = _lib.GaussUpsampleArgs()
+    g.h_ld, g.h_bs = _gu_mat(who, "h", h, B, tx, D, h.dtype)
+    g.y_ld, g.y_bs = _gu_mat(who, "y", y, B, n_out, D, h.dtype, out=True)
+    if center is None or prec is None or lse is None:
+        raise ValueError(f"{who}: center, prec and lse are required")
+    g.p_ld = _rows(who, "center", center, torch.float32, rows=B, min_cols=tx, err=ValueError)
+    for name, t in (("prec", prec), ("bias", bias)) + tuple(vectors):
+        if t is not None and _rows(who, name, t, torch.float32, rows=B, min_cols=tx, err=ValueError) != g.p_ld:
+            raise ValueError(f"{who}: {name} must have center's row stride ({g.p_ld})")
+    g.lse_ld = _rows(who, "lse", lse, torch.float32, rows=B, min_cols=n_out, err=ValueError)
+    for name, t in (("q_len", q_len), ("key_len", key_len)):
+        _vec(who, name, t, B, torch.int32, exact=True, err=ValueError)
+    g.h, g.center, g.prec, g.bias = h.data_ptr(), center.data_ptr(), prec.data_ptr(), ptr(bias)
+    g.y, g.lse, g.q_len, g.key_len = y.data_ptr(), lse.data_ptr(), ptr(q_len), ptr(key_len)
+    g.batch, g.tx, g.n_out, g.dim, g.dtype, g.offset = B, tx, n_out, D, dt(h), offset
+    return g
+
+
+def gauss_upsample_fwd(h, center, prec, y, lse, bias=None, q_len=None, key_len=None, offset=0.0):
+    """Gaussian upsampling (tt2_gauss_upsample_fwd; include/tt2_capi.h has the definition):
+    y[b, n, :] = sum_t W[n, t] h[b, t, :] with W[n, .] = softmax_t(bias[t] - prec[t] (n + offset -
+    center[t])^2) over t < key_len[b], and lse[b, n] its log-sum-exp; rows at and past q_len[b] are +0.
+    h [B, Tx, D] and y [B, n_out, D], both f32 or both bf16, may be slices of wider buffers; center,
+    prec and bias (optional) f32 [B, >= Tx] of one row stride; lse f32 [B, >= n_out]; q_len / key_len
+    [B] int32 (None: n_out / Tx).  On the current stream, no host synchronisation.  Deterministic."""
+    who = "gauss_upsample_fwd"
+    g = _gu_args(who, h, center, prec, bias, y, lse, q_len, key_len, offset)
+    _same_gpu(who, (h, center, prec, bias, y, lse, q_len, key_len), err=ValueError)
+    check(lib().tt2_gauss_upsample_fwd(C.byref(g), stream_ptr()), "tt2_gauss_upsample_fwd")
+    return y, lse
+
+
+def gauss_upsample_bwd(h, center, prec, y, lse, dy, dh=None, dcenter=None, dprec=None, dbias=None, bias=None,
+                       q_len=None, key_len=None, offset=0.0, workspace=None):
+    """The gradients of gauss_upsample_fwd (tt2_gauss_upsample_bwd) from dy [B, n_out, D] and the y and
+    lse the forward left: dh [B, Tx, D] (h's dtype), dcenter, dprec and dbias f32 [B, >= Tx] of center's
+    row stride, each optional (at least one), each +0 at and past key_len[b] and the same bits
+    whichever others are asked for.  workspace: a Workspace (default: the module's).  On the current
+    stream, no host synchronisation.  Deterministic."""
+    who = "gauss_upsample_bwd"
+    if dh is None and dcenter is None and dprec is None and dbias is None:
+        raise ValueError(f"{who}: one of dh, dcenter, dprec and dbias is required")
+    g = _gu_args(who, h, center, prec, bias, y, lse, q_len, key_len, offset,
+                 vectors=(("dcenter", dcenter), ("dprec", dprec), ("dbias", dbias)))
+    B, tx, n_out, D = g.batch, g.tx, g.n_out, g.dim
+    if dy is None:
+        raise ValueError(f"{who}: dy is required")
+    g.dy_ld, g.dy_bs = _gu_mat(who, "dy", dy, B, n_out, D, h.dtype)
+    if dh is not None:
+        g.dh_ld, g.dh_bs = _gu_mat(who, "dh", dh, B, tx, D, h.dtype, out=True)
+    _same_gpu(who, (h, center, prec, bias, y, lse, dy, dh, dcenter, dprec, dbias, q_len, key_len), err=ValueError)
+    g.dy, g.dh, g.dcenter, g.dprec, g.dbias = dy.data_ptr(), ptr(dh), ptr(dcenter), ptr(dprec), ptr(dbias)
+    L = lib()
+    _bind_workspace(g, L.tt2_gauss_upsample_bwd_workspace_size(B, tx, n_out, D), workspace)
+    check(L.tt2_gauss_upsample_bwd(C.byref(g), stream_ptr()), "tt2_gauss_upsample_bwd")
+    return dh, dcenter, dprec, dbias
+
+
 def _drop_into(s, drop: Drop):
     s.drop_seed, s.drop_site, s.drop_thr, s.drop_scale = drop.fields()
 
